@@ -12,14 +12,24 @@ previous step's shard is all-gathered over RCCL on a side stream while the
 next window loads (parallel/fanout.ShardedLoader: status word + data
 collective per step, failure consensus, per-slice CRC check of the last
 fan-out).  ``value`` = total bytes loaded by all ranks / max-rank
-wall time (GiB/s, weak scaling).  Also reported: p50/p99 latency of single
-4 KiB reads into HBM (QD1), the VFS control (pread → pinned → HtoD, the
-reference's ``nvme_test -f``) and a CRC32C check of the last window on the
-GPU against the host CRC of the file.
+wall time (GiB/s, weak scaling).
 
-``vs_baseline`` = value / VFS control measured in the same run: the reference
-publishes no numbers, its methodology's control is the
-baseline to beat on this machine.
+A plain run does only that: it writes the shard, warms up, times ``--steps``
+steps and prints the result line (``ms_per_step`` = one timed step).
+``--dump-outputs DIR`` also writes what the last timed step left in HBM (a
+seeded sample of the window plus its whole-window CRC32C) as ``DIR/*.npy``;
+the shard bytes depend only on the arguments, so two builds can be compared
+output for output.
+
+``--full`` adds everything else to the line: p50/p99 latency of single
+4 KiB reads into HBM (QD1), the VFS control (pread → pinned → HtoD, the
+reference's ``nvme_test -f``), the storage's own sequential rate, host and
+engine primitive costs and a CRC32C check of the last window on the GPU
+against the host CRC of the file.
+
+``vs_baseline`` (``--full``) = value / VFS control measured in the same run:
+the reference publishes no numbers, its methodology's control
+is the baseline to beat on this machine.
 """
 from __future__ import annotations
 
@@ -80,6 +90,45 @@ def fs_type(path: str) -> str:
     return typ
 
 
+DUMP_SAMPLES = 4 << 20      # window bytes sampled by --dump-outputs, split over the ranks
+
+
+def sample_offsets(window: int, world: int) -> np.ndarray:
+    """The byte offsets of a window that ``--dump-outputs`` keeps: all of a
+    small window, else a fixed seeded draw (sorted, distinct), the same on
+    every rank and in every run with the same arguments."""
+    n = max(1, DUMP_SAMPLES // max(1, world))
+    if window <= n:
+        return np.arange(window, dtype=np.int64)
+    return np.unique(np.random.default_rng(4321).integers(0, window, size=n, dtype=np.int64))
+
+
+def dump_outputs(d: str, rank: int, world: int, window, gathered, crc32c_of) -> None:
+    """``--dump-outputs``: what a caller of the timed path holds after the
+    last step, as float32 / float64 ``.npy`` files (under 64 MB in all).
+
+    ``window_sample_r<rank>.npy``  this rank's loaded window at ``window_offsets``
+    ``window_crc32c_r<rank>.npy``  CRC32C of the whole window (the GPU kernel)
+    ``gathered_sample.npy``        N > 1, rank 0: the same offsets of every
+                                   slice of the fanned-out output, (slices, n)
+    ``window_offsets.npy``         rank 0: the sampled byte offsets
+    """
+    import torch
+    os.makedirs(d, exist_ok=True)
+    W = window.numel()
+    offs = sample_offsets(W, world)
+    idx = torch.from_numpy(offs).to(window.device)
+    np.save(os.path.join(d, f"window_sample_r{rank}.npy"),
+            window[idx].to(torch.float32).cpu().numpy())
+    np.save(os.path.join(d, f"window_crc32c_r{rank}.npy"),
+            np.array([crc32c_of(window)], dtype=np.float64))
+    if rank == 0:
+        np.save(os.path.join(d, "window_offsets.npy"), offs.astype(np.float64))
+        if gathered is not None:
+            g = gathered.view(-1, W)[:, idx]
+            np.save(os.path.join(d, "gathered_sample.npy"), g.to(torch.float32).cpu().numpy())
+
+
 def _free_port() -> int:
     import socket
     s = socket.socket()
@@ -137,6 +186,11 @@ def main() -> int:
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process group backend (nccl = RCCL; gloo rehearses the multi-rank "
                          "path with several ranks on one GPU, collectives staged via the host)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beside the headline: QD1 4 KiB "
+                         "latencies, VFS control, storage rate, primitive costs, CRC check")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step left in HBM as DIR/<name>.npy")
     a = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -239,7 +293,7 @@ def main() -> int:
             fd, mreq, max(64, 4 * W // mreq), threads=nw, qd=min(256, max(1, qd)),
             sequential=True, fixed=fx)[1] for fx in (False, True)}
 
-    seq_pre = storage_seq()
+    seq_pre = storage_seq() if a.full else {}
     for i in range(a.warmup):
         ld.step(i)
     ld.flush()
@@ -268,10 +322,80 @@ def main() -> int:
     per_rank = ld.report(wall_s=dt)
     st = ld.stats
     agg = dict(nr_ram=st.nr_ram, nr_ssd=st.nr_ssd, nr_submit=st.nr_submit, nr_blocks=st.nr_blocks)
+    last = a.warmup + a.steps - 1
+    ing = S.ingest_info(local_dev)
+    io_path = ("P2P: NVMe READ -> HBM BAR (kernel provider)" if S.provider() == "kernel" else
+               "host-bounce (userspace provider): O_DIRECT read -> pinned staging -> "
+               + ("GPU ingest grid" if ing and ing["available"] else "SDMA copy") + " -> HBM")
+    config = {
+        "model": f"ssd2gpu_stream(segment={a.segment_mib}MiB x depth {a.depth}, chunk={a.chunk}B)",
+        "global_batch": world * W,
+        "seq_len": a.chunk,
+        "parallelism": f"dp{world}" + (f"+{mode}" if fan else ""),
+        "window_bytes_per_rank": W,
+        "file_bytes_per_rank": F,
+        "backend": S.config_get("backend"),
+        "workers": int(S.config_get("workers")),
+        "placement": placement,
+        "max_request": int(S.config_get("max_request")),
+        "engine": {k: S.config_get(k) for k in ("queue_depth", "staging_slots", "stage_by_bytes",
+                                                 "slot_lifo", "ingest", "ingest_grid",
+                                                 "ingest_piece", "fixed_bufs")},
+    }
+
+    def finish() -> int:
+        ld.close()
+        os.close(fd)
+        if not a.keep:
+            try:
+                os.unlink(path)
+            except OSError:
+                pass
+        if world > 1:
+            dist.destroy_process_group()
+        return 0
+
+    # what the timed path left behind, before anything else touches the buffers
+    if a.dump_outputs:
+        from nvme_strom_amd.parallel.fanout import crc32c_of
+        dump_outputs(a.dump_outputs, rank, world, ld.current(last), ld.out, crc32c_of)
+
+    if not a.full:
+        # a plain run ends here: the headline and what it cost nothing to know
+        out = {
+            "metric": METRIC,
+            "value": round(value, 3),
+            "unit": "GiB/s",
+            "n_gpus": world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "ms_per_step": round(tmax / a.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "full": False,
+            "storage": {"fs_type": fstype, "dir": a.dir, "path": io_path,
+                        "file_bytes_per_rank": F,
+                        "bytes_read_per_rank": (a.warmup + a.steps) * W,
+                        "windows_reread": max(0, (a.warmup + a.steps) - nwin)},
+            "rccl": {"world_size": world, "backend": dist.get_backend() if world > 1 else None,
+                     "collective": mode, "staged_via_host": ld.staged,
+                     "delivered_steps": delivered["steps"], "delivered_bytes": delivered["bytes"],
+                     "per_step_slice_check": bool(fan and a.verify_each)},
+            "per_rank": per_rank,
+            "ingest_grid": ing,
+            "avg_request_kib": round(0.5 * agg["nr_blocks"] / agg["nr_submit"], 1) if agg["nr_submit"] else 0,
+            "ram_chunks": agg["nr_ram"],
+            "ssd_chunks": agg["nr_ssd"],
+            "dtype": "uint8",
+            "data": "synthetic random-byte shard file per rank (O_DIRECT reads)",
+            "config": config,
+        }
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        return finish()
 
     # integrity of the last loaded window, and of every slice of the last
     # fan-out (collective CRC check, not timed)
-    last = a.warmup + a.steps - 1
     verified = ld.verify(last)
     gather_ok = verified if fan else None
     buf = ld.bufs[last % len(ld.bufs)]
@@ -370,7 +494,6 @@ def main() -> int:
         seq_total = seq_gib
     ver = 1.0 if verified else 0.0
     hist = S.stat_hist()
-    ing = S.ingest_info(local_dev)
     steps_bytes = (a.warmup + a.steps) * W
     out = {
         "metric": METRIC,
@@ -408,9 +531,7 @@ def main() -> int:
         "storage": {
             "fs_type": fstype,
             "dir": a.dir,
-            "path": ("P2P: NVMe READ -> HBM BAR (kernel provider)" if S.provider() == "kernel" else
-                     "host-bounce (userspace provider): O_DIRECT read -> pinned staging -> "
-                     + ("GPU ingest grid" if ing and ing["available"] else "SDMA copy") + " -> HBM"),
+            "path": io_path,
             "note": ("backing store answers 4 KiB O_DIRECT reads in "
                      f"{raw_p50:.1f} us: RAM-class, not NAND"
                      if raw_p50 == raw_p50 and raw_p50 < 20 else "device-class latency"),
@@ -438,34 +559,12 @@ def main() -> int:
         "ssd_chunks": agg["nr_ssd"],
         "dtype": "uint8",
         "data": "synthetic random-byte shard file per rank (O_DIRECT reads)",
-        "config": {
-            "model": f"ssd2gpu_stream(segment={a.segment_mib}MiB x depth {a.depth}, chunk={a.chunk}B)",
-            "global_batch": world * W,
-            "seq_len": a.chunk,
-            "parallelism": f"dp{world}" + (f"+{mode}" if fan else ""),
-            "window_bytes_per_rank": W,
-            "file_bytes_per_rank": F,
-            "backend": S.config_get("backend"),
-            "workers": int(S.config_get("workers")),
-            "placement": placement,
-            "max_request": int(S.config_get("max_request")),
-            "engine": {k: S.config_get(k) for k in ("queue_depth", "staging_slots", "stage_by_bytes",
-                                                     "slot_lifo", "ingest", "ingest_grid",
-                                                     "ingest_piece", "fixed_bufs")},
-        },
+        "config": config,
+        "full": True,
     }
     if rank == 0:
         print(json.dumps(out), flush=True)
-    ld.close()
-    os.close(fd)
-    if not a.keep:
-        try:
-            os.unlink(path)
-        except OSError:
-            pass
-    if world > 1:
-        dist.destroy_process_group()
-    return 0
+    return finish()
 
 
 if __name__ == "__main__":

@@ -16,10 +16,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run_bench(tmp_path, *extra):
+def _run_bench(tmp_path, *extra, full=True):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
            "--window-mib", "64", "--file-gib", "0.25", "--lat-samples", "100",
-           "--dir", str(tmp_path), *extra]
+           "--dir", str(tmp_path), *(["--full"] if full else []), *extra]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -49,3 +49,36 @@ def test_bench_single_rank_contract(tmp_path):
         assert k in out, k
     assert out["n_gpus"] == 1 and out["steps"] == 2 and out["warmup"] == 1
     assert out["verified_crc32c"] is True and out["value"] > 0
+    assert out["full"] is True
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_window(tmp_path):
+    """A plain run reports the headline only, and ``--dump-outputs`` writes
+    the bytes the last timed step left in HBM: they equal the shard file's."""
+    import numpy as np
+    dump = tmp_path / "dump"
+    out = _run_bench(tmp_path, "--keep", "--dump-outputs", str(dump), full=False)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+        assert k in out, k
+    assert out["full"] is False and out["steps"] == 2 and out["value"] > 0
+    W = 64 << 20
+    assert abs(out["ms_per_step"] - W / (out["value"] * (1 << 30)) * 1e3) < 0.01 * out["ms_per_step"]
+    # nothing of the other measurements ran
+    for k in ("vs_baseline", "vfs_control_GiBps", "storage_seq_GiBps", "p50_4k_lat_us",
+              "host_costs_ns", "verified_crc32c"):
+        assert k not in out, k
+    offs = np.load(dump / "window_offsets.npy")
+    got = np.load(dump / "window_sample_r0.npy")
+    crc = np.load(dump / "window_crc32c_r0.npy")
+    assert got.dtype == np.float32 and offs.dtype == np.float64 and crc.dtype == np.float64
+    assert sum(f.stat().st_size for f in dump.iterdir()) <= 64_000_000
+    # steps 0..2 of a 4-window shard: the last timed step loaded window 2
+    shard = np.fromfile(tmp_path / "shard_r0.bin", dtype=np.uint8)
+    assert shard.size == 4 * W
+    win = shard[2 * W:3 * W]
+    idx = offs.astype(np.int64)
+    assert len(idx) == len(got) > 1 << 20 and (np.diff(idx) > 0).all() and idx[-1] < W
+    assert np.array_equal(got, win[idx].astype(np.float32))
+    import nvme_strom_amd as S
+    assert int(crc[0]) == S.crc32c_host(win.tobytes())

@@ -46,6 +46,26 @@ def test_bench_shard_sizing():
     assert b.shard_bytes(4 * G, G, int(9.9 * G), 0, 2) == 3 * G     # whole windows
 
 
+def test_bench_dump_sample_offsets():
+    """--dump-outputs keeps the same sorted, distinct offsets in every run,
+    all of a small window, and under 64 MB of files at any rank count."""
+    import importlib.util
+    import os
+    import numpy as np
+    spec = importlib.util.spec_from_file_location(
+        "bench_mod", os.path.join(os.path.dirname(os.path.dirname(__file__)), "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert np.array_equal(b.sample_offsets(1000, 1), np.arange(1000))
+    for world in (1, 2, 8):
+        o = b.sample_offsets(1 << 30, world)
+        assert np.array_equal(o, b.sample_offsets(1 << 30, world))
+        assert o.dtype == np.int64 and (np.diff(o) > 0).all() and 0 <= o[0] and o[-1] < 1 << 30
+        assert 0.99 * (b.DUMP_SAMPLES // world) <= len(o) <= b.DUMP_SAMPLES // world
+        # float32 samples per rank + the gathered slices, float64 offsets
+        assert len(o) * (4 * world + 4 * world * (world > 1) + 8) <= 64_000_000
+
+
 def test_gpu_recipes_parse():
     """tools/gpu.sh (every committed profile's recipe) is valid bash, and the
     phases the round-6 summary cites exist in it."""

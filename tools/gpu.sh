@@ -19,7 +19,7 @@
 #   zatrace    kernel trace of the Arrow ZSTD scan per group size (ingest grid vs decoder)
 #   mtests     model-level GPU tests only (PG / Arrow / multi-rank scans)
 #   smoke      __graft_entry__.smoke()
-#   bench      python bench.py (default flagship config)
+#   bench      python bench.py --full (default flagship config, every figure)
 #   kbench     per-kernel throughput (nvme_strom_amd.tools.kbench)
 #   par        LZ4 decoder rows by stream count: lane groups vs block-parallel (lz4par)
 #   dtests     decoder numerics tests only
@@ -74,7 +74,7 @@ for phase in "$@"; do
     mtests) step mtests 300 python -u -m pytest tests/test_gpu_models.py -m gpu -x -v \
               --timeout 120 --timeout-method thread ;;
     smoke) step smoke 120 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 400 python bench.py; grep '^{' "$OUT/bench.log" | tail -1 > "$OUT/bench.json"; cat "$OUT/bench.json" ;;
+    bench) step bench 400 python bench.py --full; grep '^{' "$OUT/bench.log" | tail -1 > "$OUT/bench.json"; cat "$OUT/bench.json" ;;
     kbench) step kbench 300 python -u -m nvme_strom_amd.tools.kbench --out "$OUT/kbench.json" ;;
     zbench) step zbench 300 python -u -m nvme_strom_amd.tools.zstd_bench --out "$OUT/zstd.json" ;;
     zprof) step zprof 300 python -u -m nvme_strom_amd.tools.zstd_bench --prof --no-lz4 --streams ${ZSTREAMS:-2048} --out "$OUT/zprof.json" ;;
@@ -148,7 +148,7 @@ for phase in "$@"; do
               SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d "$OUT/pmc" -o pmc \
               -- python3 -m nvme_strom_amd.tools.kbench --gib 0.5 --only crc,heap,lz4) ;;
     btrace) (cd /tmp && step btrace 300 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d "$OUT/btrace" -o btrace \
-              -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --lat-samples 300) ;;
+              -- python3 "$ROOT/bench.py" --full --steps 3 --warmup 1 --lat-samples 300) ;;
     esweep) # engine-only sweep with worker phase attribution; ESWEEP_NAME / ESWEEP_ARGS
             nm=${ESWEEP_NAME:-esweep}
             step $nm 500 python -u -m nvme_strom_amd.tools.sweep --engine-only --prof --no-lat \
@@ -197,7 +197,7 @@ for phase in "$@"; do
         for arm in ${BENCHAB:-def:}; do
           i=$((i + 1)); name=${arm%%:*}; kv=${arm#*:}; envs=()
           for x in ${kv//,/ }; do envs+=("STROM_$x"); done
-          step "bench_${i}_$name" 300 env "${envs[@]}" python -u bench.py
+          step "bench_${i}_$name" 300 env "${envs[@]}" python -u bench.py --full
           grep '^{' "$OUT/bench_${i}_$name.log" | tail -1 > "$OUT/bench_${i}_$name.json"
         done
       done ;;

@@ -595,6 +595,64 @@ int strom_bitmap_to_rows_str(const uint64_t *d_bitmap, uint64_t nwords,
                              int64_t *d_poff, uint8_t *d_pchars, uint8_t *d_pvalid,
                              uint64_t *d_char_cursor, void *stream);
 
+/* Aggregates over the selection bitmap (csrc/kernels/colagg.hip; Arrow
+ * scans: ArrowScan.aggregate): COUNT / SUM / MIN / MAX of one column's
+ * selected valid rows, per key slot when a key column is given.
+ *
+ * One entry = one aggregated column: popcount(ops) accumulator arrays of
+ * nslots 64-bit words each, in the order COUNT, SUM, MIN, MAX.  SUM holds an
+ * int64/uint64 (wrapping) or, for F32/F64, a double.  MIN / MAX hold
+ * order-preserving keys: signed integers x ^ 2^63, unsigned x, floats (as
+ * doubles) with the sign bit set for x >= 0 and all bits flipped for x < 0;
+ * NaN never enters them (MIN key > MAX key with COUNT > 0: every value was NaN).
+ * type STROM_COL_NONE: only the column's validity is read (COUNT of any
+ * column kind); with STROM_AGG_ALL not even that (count(*)).
+ *
+ * Keys: key_type one of the integer STROM_COL_* (the slot is the value, a
+ * dictionary index) or STROM_COL_BOOL; slots [0, nslots - 1) are the key
+ * values, slot nslots - 1 the null keys.  A selected row whose key is
+ * negative or >= nslots - 1 adds one to *d_bad_keys (when given: one launch of
+ * a query counts them) and nothing else.
+ * d_keys == NULL: nslots must be 1.  A launch's accumulators live in LDS:
+ * popcount(ops) * nslots * 8 <= STROM_AGG_LDS_BYTES, else -7.
+ *
+ * strom_column_agg writes one partial slab per workgroup (strom_column_agg_grid
+ * of them, popcount(ops) * nslots words each) to d_slabs — no global float
+ * atomics; strom_column_agg_reduce folds the slabs into the entry at d_acc in
+ * a fixed order (the same geometry gives the same bits for an unkeyed float
+ * sum).  strom_column_agg_init sets an entry to its identities. */
+#define STROM_COL_NONE 0
+#define STROM_AGG_COUNT 1
+#define STROM_AGG_SUM 2
+#define STROM_AGG_MIN 4
+#define STROM_AGG_MAX 8
+#define STROM_AGG_ALL 16       /* ignore the column's validity (count(*)) */
+#define STROM_AGG_LDS_BYTES (64u << 10)
+int strom_column_agg_init(uint32_t ops, uint32_t nslots, uint64_t *d_acc, void *stream);
+uint32_t strom_column_agg_grid(uint64_t nwords, uint32_t ops, uint32_t nslots);
+int strom_column_agg(int type, uint32_t ops, const uint64_t *d_bitmap, uint64_t nwords,
+                     const struct strom_filter_batch *d_vals,
+                     const struct strom_filter_batch *d_keys, int key_type, uint32_t nslots,
+                     uint32_t nbatches, uint64_t *d_slabs, uint64_t slab_words,
+                     uint64_t *d_bad_keys, void *stream);
+int strom_column_agg_reduce(int type, uint32_t ops, uint32_t nslots, const uint64_t *d_slabs,
+                            uint32_t nslabs, uint64_t *d_acc, void *stream);
+/* All entries of a query over one group in one call each: launch i writes
+ * e[i].slabs (sized by strom_column_agg_grid), reduce i folds them into
+ * e[i].acc; malformed keys are counted by entry 0's launch only. */
+struct strom_agg_entry {
+	int32_t type;
+	uint32_t ops;
+	uint64_t vals;         /* device strom_filter_batch table of the column */
+	uint64_t slabs;
+	uint64_t acc;          /* the entry's words in the accumulator block */
+};
+int strom_column_agg_many(const struct strom_agg_entry *e, uint32_t n, const uint64_t *d_bitmap,
+                          uint64_t nwords, const struct strom_filter_batch *d_keys, int key_type,
+                          uint32_t nslots, uint32_t nbatches, uint64_t *d_bad_keys, void *stream);
+int strom_column_agg_reduce_many(const struct strom_agg_entry *e, uint32_t n, uint32_t nslots,
+                                 uint64_t nwords, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

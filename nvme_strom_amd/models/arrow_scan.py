@@ -39,10 +39,11 @@ import numpy as np
 import torch
 
 from .. import api
+from ..ops import colagg as A
 from ..ops import decompress as D
 from ..ops.colfilter import BATCH_FIELDS, bitmap_to_rows, bitmap_to_rows_str
-from ..ops.colpred import (QUAL_BATCH_FIELDS, Compiled, Pred, clauses, compile_pred, evaluate,
-                           qual_batched)
+from ..ops.colpred import (COL_CODE, QUAL_BATCH_FIELDS, Compiled, Pred, clauses, compile_pred,
+                           evaluate, qual_batched)
 from ..ops.reorder import chunk_scatter, landing_positions
 from ..tensor import FileReader, HbmBuffer, host_buffer
 from ..utils.arrow_ipc import (ArrowFile, Column, _Src, decode_values, dictionary_values,
@@ -146,6 +147,7 @@ class _Group:
     # records in file order with their slot offsets, the slot span they take
     # and the bytes the reads cover (buffers + holes read through + padding)
     ext: Optional[np.ndarray] = None
+    ones: Optional[np.ndarray] = None       # every row selected (aggregate without qualifiers)
     span: int = 0
     read_bytes: int = 0
     gap_bytes: int = 0
@@ -707,9 +709,11 @@ class ArrowScan:
             # one batch table per referenced column, uploaded once per group
             tabs: Dict[int, torch.Tensor] = {}
 
+            tabs_np: Dict[int, np.ndarray] = {}
+
             def table(col: int) -> torch.Tensor:
                 if col not in tabs:
-                    t = self._pointers(g, col, base, dec_base)
+                    t = tabs_np[col] = self._pointers(g, col, base, dec_base)
                     tabs[col] = self._upload(s, t)
                     s.keep.append(tabs[col])
                 return tabs[col]
@@ -734,10 +738,48 @@ class ArrowScan:
                     else:
                         qual_batched(cq, table(col), g.words, s.bitmap, cnt, stream=cs,
                                      or_src=s.bm2, and_dst=True)
+            bitmap = s.bitmap
+            if not spec:
+                # no qualifier (aggregate only): every row of every batch,
+                # each batch's last word bounded by its rows
+                if g.ones is None:
+                    g.ones = _all_rows_bitmap(g.table[:, 2])
+                bitmap = self._upload(s, g.ones)
+                s.keep.append(bitmap)
             state["marks"].append((k, "quals_queued", time.perf_counter()))
             # emit tables: the strom_filter_batch prefix of the qual tables
-            any_col = spec[0][0][0]
+            any_col = spec[0][0][0] if spec else 0
             d_rows = table(any_col)[:, :BATCH_FIELDS].contiguous()
+            agg = state.get("agg")
+            if agg is not None:
+                # one aggregate launch per aggregated column on the slot's
+                # stream, each leaving its workgroups' slabs.  The host's time
+                # here delays the next group's read: the columns' batch
+                # tables go up in one copy, the slabs are one allocation and
+                # the launches one native call
+                lay = agg.layout
+                n = len(g.table)
+                cols = sorted({any_col if c is None else c for c in agg.entry_cols} |
+                              ({agg.key_col} if agg.key_col is not None else set()))
+                t5 = np.stack([(tabs_np[c] if c in tabs_np else
+                                self._pointers(g, c, base, dec_base))[:, :BATCH_FIELDS]
+                               for c in cols])
+                d_t5 = self._upload(s, t5)
+                at = {c: d_t5.data_ptr() + i * n * BATCH_FIELDS * 8 for i, c in enumerate(cols)}
+                if g.words not in agg.slab_words:
+                    agg.slab_words[g.words] = [A.slab_words(lay, e, g.words)
+                                               for e in range(len(lay.entries))]
+                sw = agg.slab_words[g.words]
+                d_slabs = torch.empty(sum(sw), dtype=torch.int64, device=self.device)
+                s.keep += [d_t5, d_slabs]
+                args = A.entry_args(lay, state["block"])
+                o = d_slabs.data_ptr()
+                for e, c in enumerate(agg.entry_cols):
+                    args[e].vals = at[any_col if c is None else c]
+                    args[e].slabs = o
+                    o += 8 * sw[e]
+                A.agg_many(lay, args, state["block"], bitmap, g.words,
+                           at[agg.key_col] if agg.key_col is not None else 0, n, stream=cs)
             pstr = state.get("pchars") is not None
             d_proj = None
             if proj is not None:
@@ -751,7 +793,10 @@ class ArrowScan:
         es = self.emit_stream
         es.wait_event(ready)
         with torch.cuda.stream(es):
-            if pstr:
+            if agg is not None:
+                # the slabs into the scan's accumulator block, in group order
+                A.agg_reduce_many(agg.layout, args, g.words, stream=es)
+            elif pstr:
                 bitmap_to_rows_str(s.bitmap, g.words, d_rows, state["out"], state["cursor"],
                                    d_proj, state["owidth"], state["poff"], state["pchars"],
                                    state["ccursor"], pvalid=state.get("pvalid"), stream=es)
@@ -902,6 +947,100 @@ class ArrowScan:
                        valid=pvalid[:count] if pvalid is not None else None,
                        column=pmeta, dictionary=pdict, offsets=offsets)
 
+    def aggregate(self, quals, aggs, by: Optional[str] = None,
+                  batches: Optional[Tuple[int, int]] = None) -> "AggOut":
+        """``SELECT by, aggs... WHERE quals GROUP BY by`` in one pass over
+        the file: the qualifier, aggregated and key columns are read and
+        decoded once per group, the qualifier kernels leave the selection
+        bitmap and the aggregate kernels (csrc/kernels/colagg.hip) consume
+        it on the slot's stream — no row ids are written, a few kilobytes of
+        accumulators stay on the device until the scan's one sync.
+
+        ``quals`` as in scan_where; an empty list selects every row.
+        ``aggs``: ``(fn, column)`` with fn ``count`` (column None: count(*)),
+        ``sum``, ``min``, ``max``, ``mean``.  sum / min / max take integer
+        and float columns, min / max also date / time / timestamp / duration
+        (their ticks); count takes any column.  Integer sums wrap in 64
+        bits, float sums are float64; NaN propagates into a sum and is
+        ignored by min / max; nulls are skipped.  ``by``: a
+        dictionary-encoded, bool or 8-bit integer column (null keys form a
+        group of their own, key None).  See AggOut."""
+        t0 = time.perf_counter()
+        cl = clauses(quals) if quals else []
+        agg = _agg_spec(self.meta, aggs, by, self.dictionary)
+        names: List[str] = []
+        for n in [p.col for c in cl for p in c] + agg.names:
+            if n not in names:
+                names.append(n)
+        nb = self.meta.nbatches
+        rng = (0, nb) if batches is None else (max(0, int(batches[0])), min(nb, int(batches[1])))
+        if not names:
+            # count(*) of everything: the footer answers
+            block = A.new_block(agg.layout)
+            nrows = int(np.asarray(self.meta.rows)[rng[0]:max(rng[0], rng[1])].sum())
+            block[agg.layout.pos(0, A.COUNT)] = np.uint64(nrows)
+            return _agg_out(agg, block, nrows, {"total_s": time.perf_counter() - t0})
+        key = (tuple(names), rng)
+        if key not in self._plans:
+            if tuple(names) not in self._bplans:
+                self._bplans[tuple(names)] = self._plan(names)
+            allb, cols, _ = self._bplans[tuple(names)]
+            sel = allb[rng[0]:max(rng[0], rng[1])]
+            self._plans[key] = (cols, int(sel.rows.sum()) if len(sel) else 0, self._groups(sel))
+        cols, nrows, groups = self._plans[key]
+        spec = [[(names.index(p.col), self._compile(p)) for p in c] for c in cl]
+        t_plan = time.perf_counter()
+        if not groups or nrows == 0:
+            return _agg_out(agg, A.new_block(agg.layout), nrows,
+                            {"total_s": time.perf_counter() - t0})
+        agg.entry_cols = [None if n is None else names.index(n) for n in agg.entry_names]
+        agg.key_col = names.index(by) if by is not None else None
+        self._ensure_slots(groups)
+        if getattr(self, "emit_stream", None) is None:
+            self.emit_stream = torch.cuda.Stream(device=self.device)
+        z = lambda: torch.zeros(1, dtype=torch.int64, device=self.device)
+        # the block is initialised on the emit stream, where the reduces follow
+        with torch.cuda.stream(self.emit_stream):
+            block = A.alloc_block(agg.layout, self.device, stream=self.emit_stream)
+        state = dict(agg=agg, block=block, count=z(), err=z(), wait_s=0.0, bytes_read=0,
+                     column_bytes=0, marks=[])
+        # the aggregate launches (slot streams) count malformed keys in the
+        # block: they must see it initialised
+        ready = torch.cuda.Event()
+        ready.record(self.emit_stream)
+        state["block_ready"] = ready
+        t_alloc = time.perf_counter()
+        ahead = max(1, min(self.nslots, len(self._slots)) - 1)
+        for k in range(min(ahead, len(groups))):
+            self._submit(k, groups[k])
+        for k in range(len(groups)):
+            self._slots[k % len(self._slots)].stream.wait_event(ready)
+            self._compute(k, spec, None, state)
+            if k + ahead < len(groups):
+                self._submit(k + ahead, groups[k + ahead])
+        torch.cuda.synchronize(self.device)
+        err = int(state["err"].item())
+        host = A.block_to_host(block)
+        t_end = time.perf_counter()
+        for s in self._slots:
+            s.keep = []
+            s.event = None
+        if err:
+            raise RuntimeError(f"{'ZSTD' if self._codec == D.ARROW_ZSTD else 'LZ4'} decode "
+                               f"failed for {err} buffer(s) of columns {names}")
+        return _agg_out(agg, host, nrows,
+                        {"plan_s": t_plan - t0, "alloc_s": t_alloc - t_plan,
+                         "wait_s": state["wait_s"], "total_s": t_end - t0},
+                        bytes_read=state["bytes_read"], column_bytes=state["column_bytes"],
+                        groups=len(groups))
+
+    def host_aggregate(self, quals, aggs, by: Optional[str] = None,
+                       batches: Optional[Tuple[int, int]] = None) -> "AggOut":
+        """The same query on the CPU (host_scan_where's path plus the
+        aggregate kernels' numpy twin, ops/colagg.py)."""
+        return host_aggregate(self.path, quals, aggs, by, batches, meta=self.meta,
+                              dicts=self._dicts)
+
     def scan(self, name: str, lo, hi) -> ScanOut:
         """Row ids (int64, file order) of ``lo <= column <= hi`` (nulls never
         qualify)."""
@@ -1016,3 +1155,271 @@ def host_scan_where(path: str, quals, project: Optional[str] = None,
         vv = np.concatenate(valid) if valid else np.zeros(0, bool)
         out.valid = None if vv.all() else vv
     return out
+
+
+# ------------------------------------------------------------ aggregation
+_AGG_FNS = {"count": A.COUNT, "sum": A.SUM, "min": A.MIN, "max": A.MAX, "mean": A.SUM}
+_TEMPORAL = ("date", "time", "timestamp", "duration")
+
+
+def _all_rows_bitmap(rows: np.ndarray) -> np.ndarray:
+    """The bitmap that selects every row: each batch on fresh words, its
+    last word bounded by its rows."""
+    rows = np.asarray(rows, np.int64)
+    words = (rows + 63) // 64
+    out = np.full(int(words.sum()), 0xFFFFFFFFFFFFFFFF, np.uint64)
+    last = np.cumsum(words) - 1
+    tail = rows % 64
+    m = (tail != 0) & (words > 0)
+    out[last[m]] = (np.uint64(1) << tail[m].astype(np.uint64)) - np.uint64(1)
+    return out.view(np.int64)
+
+
+@dataclass
+class _AggSpec:
+    aggs: List[Tuple[str, Optional[str]]]
+    by: Optional[str]
+    layout: A.Layout
+    entry_names: List[Optional[str]]        # entry 0: count(*), then one per column
+    names: List[str]                        # columns the aggregation reads
+    cols: Dict[str, Column]
+    keyvals: Optional[list] = None          # key of each non-null slot
+    entry_cols: Optional[List[Optional[int]]] = None    # plan column of each entry (GPU)
+    key_col: Optional[int] = None
+    slab_words: Dict[int, List[int]] = field(default_factory=dict)   # by group words
+
+
+def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary) -> _AggSpec:
+    """Validate ``aggs`` / ``by`` against the schema and lay the accumulator
+    block out: entry 0 counts the selected rows per slot, then one entry per
+    aggregated column with COUNT and whatever of SUM / MIN / MAX is asked."""
+    schema = {c.name: c for c in meta.schema}
+    aggs = [(str(fn), col) for fn, col in aggs]
+    if not aggs:
+        raise ValueError("at least one aggregate")
+    ops: Dict[str, int] = {}
+    for fn, col in aggs:
+        if fn not in _AGG_FNS:
+            raise ValueError(f"aggregate {fn!r}: one of {sorted(_AGG_FNS)}")
+        if col is None:
+            if fn != "count":
+                raise ValueError(f"{fn} needs a column")
+            continue
+        if col not in schema:
+            raise ValueError(f"no column {col!r}")
+        c = schema[col]
+        if not c.supported:
+            raise NotImplementedError(f"column {col}: {c.kind} columns are not scanned on the GPU")
+        if fn != "count":
+            kind = "dictionary-encoded" if c.dictionary is not None else c.kind
+            if c.dictionary is not None or c.kind in ("utf8", "binary", "bool", "decimal") or \
+                    c.storage not in A.VALUE_CODE:
+                raise NotImplementedError(f"{fn}({col}): {kind} columns have count only")
+            if c.kind in _TEMPORAL and fn in ("sum", "mean"):
+                raise NotImplementedError(f"{fn}({col}): {c.kind} columns have min, max and count")
+        ops[col] = ops.get(col, A.COUNT) | _AGG_FNS[fn]
+    nslots, key_code, keyvals = 1, 0, None
+    if by is not None:
+        if by not in schema:
+            raise ValueError(f"no column {by!r}")
+        k = schema[by]
+        if k.dictionary is not None:
+            vals, dvalid = dictionary(by)
+            if isinstance(vals, tuple):
+                offs, chars = vals
+                raw = [chars[offs[i]:offs[i + 1]].tobytes() for i in range(len(offs) - 1)]
+                keyvals = [r.decode() for r in raw] if k.kind == "utf8" else raw
+            else:
+                keyvals = np.asarray(vals).tolist()
+            if dvalid is not None:
+                keyvals = [v if ok else None for v, ok in zip(keyvals, dvalid)]
+            key_code = COL_CODE[k.storage]
+        elif k.kind == "bool":
+            keyvals, key_code = [False, True], A.COL_BOOL
+        elif k.kind == "int" and k.bit_width == 8:
+            # the slot is the value's byte
+            b = np.arange(256, dtype=np.uint8)
+            keyvals = (b.view(np.int8) if k.signed else b).tolist()
+            key_code = COL_CODE["u1"]
+        else:
+            raise NotImplementedError(
+                f"GROUP BY {by}: {k.kind} keys (dictionary-encoded, bool and 8-bit integer "
+                "columns are grouped on the GPU)")
+        nslots = len(keyvals) + 1
+    entries = [A.Entry(A.COUNT | A.ALL)]
+    entry_names: List[Optional[str]] = [None]
+    for col, o in ops.items():
+        entries.append(A.Entry(o, schema[col].storage if o != A.COUNT else None, col))
+        entry_names.append(col)
+    names = [n for n in entry_names[1:]]
+    if by is not None and by not in names:
+        names.append(by)
+    return _AggSpec(aggs, by, A.Layout(entries, nslots, key_code), entry_names, names,
+                    {n: schema[n] for n in names}, keyvals)
+
+
+@dataclass
+class AggOut:
+    """Result of ArrowScan.aggregate / host_aggregate (host side, numpy).
+
+    One row per group that selected anything, in slot order (dictionary
+    index / False, True / byte value), the null-key group last; without
+    ``by`` exactly one row.  ``values[i]`` / ``valid[i]`` belong to
+    ``aggs[i]``: sums are int64 / uint64 / float64, min and max have the
+    column's storage dtype (ticks for temporal columns: ``columns[i]`` holds
+    the type), mean is float64(sum) / count; a group whose column counted
+    nothing has an invalid sum, min, max and mean."""
+    rows: int
+    selected: int
+    aggs: List[Tuple[str, Optional[str]]]
+    by: Optional[str]
+    keys: Optional[list]
+    count_all: np.ndarray
+    values: List[np.ndarray]
+    valid: List[np.ndarray]
+    columns: List[Optional[Column]]
+    seconds: Dict[str, float]
+    bytes_read: int = 0
+    column_bytes: int = 0
+    groups: int = 0
+    _spec: Optional[_AggSpec] = None
+    _block: Optional[np.ndarray] = None
+
+    def get(self, fn: str, col: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """(values, valid) of one requested aggregate."""
+        i = self.aggs.index((fn, col))
+        return self.values[i], self.valid[i]
+
+    def merge(self, other: "AggOut") -> "AggOut":
+        """This result combined with another over the same ``aggs`` and
+        ``by`` of the same file (other record batches, another rank):
+        counts and sums add, min and max combine."""
+        a, b = self._spec, other._spec
+        if a.aggs != b.aggs or a.by != b.by or a.layout.nslots != b.layout.nslots or \
+                a.keyvals != b.keyvals:
+            raise ValueError("merge: different aggregates, key or dictionary")
+        secs = {"total_s": self.seconds.get("total_s", 0.0) + other.seconds.get("total_s", 0.0)}
+        return _agg_out(a, A.merge_blocks(a.layout, self._block, other._block),
+                        self.rows + other.rows, secs,
+                        bytes_read=self.bytes_read + other.bytes_read,
+                        column_bytes=self.column_bytes + other.column_bytes,
+                        groups=self.groups + other.groups)
+
+
+def _agg_out(spec: _AggSpec, block: np.ndarray, rows: int, seconds: Dict[str, float],
+             bytes_read: int = 0, column_bytes: int = 0, groups: int = 0) -> AggOut:
+    lay = spec.layout
+    bad = int(block[0])
+    if bad:
+        raise RuntimeError(f"key column {spec.by}: {bad} selected row(s) with an index outside "
+                           f"its dictionary of {lay.nslots - 1} entries")
+    count_all = A.entry_arrays(lay, block, 0)["count"]
+    if spec.by is None:
+        show = np.zeros(1, np.int64)
+        keys = None
+    else:
+        show = np.flatnonzero(count_all > 0)
+        keys = [spec.keyvals[s] if s < lay.nslots - 1 else None for s in show.tolist()]
+    ent = {n: A.entry_arrays(lay, block, e) for e, n in enumerate(spec.entry_names) if e}
+    values, valid, columns = [], [], []
+    for fn, col in spec.aggs:
+        if col is None:
+            values.append(count_all[show])
+            valid.append(np.ones(len(show), bool))
+            columns.append(None)
+            continue
+        a = ent[col]
+        cnt = a["count"][show]
+        has = cnt > 0
+        if fn == "count":
+            v, ok = cnt, np.ones(len(show), bool)
+        elif fn == "mean":
+            v = np.full(len(show), np.nan)
+            np.divide(a["sum"][show].astype(np.float64), cnt, out=v, where=has)
+            ok = has
+        else:
+            v, ok = a[fn][show], has
+        values.append(v)
+        valid.append(ok)
+        columns.append(spec.cols[col])
+    return AggOut(rows, int(count_all.sum()), spec.aggs, spec.by, keys, count_all[show], values,
+                  valid, columns, seconds, bytes_read, column_bytes, groups, spec, block)
+
+
+def host_aggregate(path: str, quals, aggs, by: Optional[str] = None,
+                   batches: Optional[Tuple[int, int]] = None, meta: Optional[ArrowFile] = None,
+                   dicts: Optional[dict] = None) -> AggOut:
+    """ArrowScan.aggregate on the CPU: buffers read with pread and decoded
+    by the decoders' host twins, the qualifiers by colpred's numpy twin, the
+    aggregates by colagg's.  The reference point for the GPU path and the
+    same answer on machines without one."""
+    t0 = time.perf_counter()
+    meta = meta if meta is not None else read_metadata(path)
+    dicts = dicts if dicts is not None else {}
+    cl = clauses(quals) if quals else []
+    schema = {c.name: (i, c) for i, c in enumerate(meta.schema)}
+
+    def dictionary(name):
+        if name not in dicts:
+            dicts[name] = dictionary_values(meta, schema[name][1], path)
+        return dicts[name]
+    spec = _agg_spec(meta, aggs, by, dictionary)
+    comp = []
+    for c in cl:
+        row = []
+        for p in c:
+            if p.col not in schema:
+                raise ValueError(f"no column {p.col!r}")
+            col = schema[p.col][1]
+            dic = dictionary(p.col) if col.dictionary is not None and \
+                p.op not in ("is_null", "is_valid") else None
+            row.append((p.col, compile_pred(p, col, dic)))
+        comp.append(row)
+    names = sorted({n for c in comp for n, _ in c} | set(spec.names))
+    nb = meta.nbatches
+    b0, b1 = (0, nb) if batches is None else (max(0, batches[0]), min(nb, batches[1]))
+    lay = spec.layout
+    block = A.new_block(lay)
+    nrows = 0
+    src = _Src(path)
+    try:
+        for bi in range(b0, b1):
+            b = meta.batches[bi]
+            data = {}
+            for n in names:
+                ci, col = schema[n]
+                ch = b.columns[ci]
+                vraw = read_buffer(src, ch.validity, b.codec) if ch.null_count else b""
+                ok = validity_bits(vraw, ch.length)
+                if not any(n == q for c in comp for q, _ in c) and \
+                        n != by and lay.entries[spec.entry_names.index(n)].dtype is None:
+                    data[n] = (None, ok)          # counted only: its validity is enough
+                    continue
+                d = read_buffer(src, ch.data, b.codec)
+                vcol = col if col.dictionary is None else Column(n, "int", col.dictionary.index_bits,
+                                                                 col.dictionary.index_signed)
+                x = read_buffer(src, ch.extra, b.codec) if (ch.extra is not None and
+                                                            col.dictionary is None) else b""
+                data[n] = (decode_values(vcol, ch.length, d, x), ok)
+            n = b.length
+            nrows += n
+            m = np.ones(n, bool)
+            for c in comp:
+                cm = np.zeros(n, bool)
+                for name, cq in c:
+                    v, ok = data[name]
+                    cm |= evaluate(cq, v, ok, n)
+                m &= cm
+            key = None
+            if by is not None:
+                kv, kok = data[by]
+                kv = np.asarray(kv)
+                if kv.dtype == np.int8 and schema[by][1].dictionary is None:
+                    kv = kv.view(np.uint8)        # 8-bit key: the slot is the byte
+                key = (kv, kok)
+            for e, name in enumerate(spec.entry_names):
+                v, ok = (None, None) if name is None else data[name]
+                A.host_agg(lay, block, e, m, v, ok, key, count_bad=e == 0)
+    finally:
+        src.close()
+    return _agg_out(spec, block, nrows, {"total_s": time.perf_counter() - t0})

@@ -32,6 +32,10 @@ range, and a date range AND an OR of timestamp ranges — each verified
 against pyarrow.compute (row ids of Table.filter of the same expression),
 whose time on the memory-mapped file is ``cpu_ms``.
 
+``--agg`` adds the aggregate rows (``agg_rows``): ``ArrowScan.aggregate`` of
+count(*), sum(id), min(x), max(x) under the ``val`` and ``x`` ranges, alternated
+with ``scan_where(project="id")`` + a torch sum, and against four such scans.
+
 ``python -m nvme_strom_amd.tools.arrow_bench --out gpurun_out/arrow.json``
 """
 from __future__ import annotations
@@ -172,6 +176,98 @@ def pc_scan(path: str, quals) -> tuple:
     return time.perf_counter() - t0, ids
 
 
+def agg_rows(path: str, fd: int, a, col) -> dict:
+    """``aggregate([val range, x range], [count(*), sum(id), min(x), max(x)])``
+    alternated with what the same answer costs without it: for one of those
+    aggregates, ``scan_where(same quals, project="id")`` + ``values.sum()`` in
+    torch; for all four, four such scans (ids only for the count, ``id`` for
+    the sum, ``x`` twice for min and max).  ``--agg-pairs`` alternated runs at
+    the two selectivities of the scan rows, the order flipped every pair, the
+    file evicted before every run; ratios are medians over the pairs."""
+    import torch
+
+    import nvme_strom_amd as S
+    from nvme_strom_amd.models.arrow_scan import ArrowScan
+    aggs = [("count", None), ("sum", "id"), ("min", "x"), ("max", "x")]
+    rows = {}
+    for label, quals in (("wide", [("val", 100_000, 599_999), ("x", 0.25, 0.75)]),
+                         ("narrow", [("val", 100_000, 199_999), ("x", 0.25, 0.5)])):
+        sc = ArrowScan(path, "cuda", slot_bytes=a.slot_mib << 20, nslots=a.nslots or None,
+                       chunk_sz=(a.chunk_kib << 10) or None)
+
+        def t_agg():
+            S.evict_file(fd)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            out = sc.aggregate(quals, aggs)
+            return time.perf_counter() - t, out
+
+        def t_proj(proj, reduce):
+            S.evict_file(fd)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            out = sc.scan_where(quals, project=proj)
+            v = reduce(out)
+            return time.perf_counter() - t, v, out
+
+        def x_valid(out):
+            return out.values if out.valid is None else out.values[out.valid.bool()]
+        four = [(None, lambda o: o.selected), ("id", lambda o: int(o.values.sum().item())),
+                ("x", lambda o: float(x_valid(o).min().item())),
+                ("x", lambda o: float(x_valid(o).max().item()))]
+        try:
+            t_agg()                                   # cold runs: plans, slots, code objects
+            t_proj("id", four[1][1])
+            t_proj("x", four[2][1])
+            agg_s, proj_s, four_s = [], [], []
+            for k in range(max(1, a.agg_pairs)):
+                order = ("agg", "proj") if k % 2 == 0 else ("proj", "agg")
+                for what in order:
+                    if what == "agg":
+                        dt, out = t_agg()
+                        agg_s.append(dt)
+                    else:
+                        dt, psum, pout = t_proj("id", four[1][1])
+                        proj_s.append(dt)
+                got4, dt4 = [], 0.0
+                for proj, red in four:
+                    dt, v, _ = t_proj(proj, red)
+                    dt4 += dt
+                    got4.append(v)
+                four_s.append(dt4)
+                _log(f"agg {label} pair {k}: aggregate {agg_s[-1] * 1e3:.1f} ms, project+sum "
+                     f"{proj_s[-1] * 1e3:.1f} ms, four scans {dt4 * 1e3:.1f} ms")
+        finally:
+            sc.close()
+        m = None
+        for name, lo, hi in quals:
+            vals, valid = col(name)
+            mm = (vals >= lo) & (vals <= hi)
+            if valid is not None:
+                mm &= valid
+            m = mm if m is None else m & mm
+        xs = col("x")[0][m]
+        want = [int(m.sum()), int(col("id")[0][m].sum()), float(xs.min()), float(xs.max())]
+        got = [int(out.get("count")[0][0]), int(out.get("sum", "id")[0][0]),
+               float(out.get("min", "x")[0][0]), float(out.get("max", "x")[0][0])]
+        ratios = [x / y for x, y in zip(agg_s, proj_s)]
+        rows[label] = dict(
+            quals=[repr(q) for q in quals], aggs=[list(x) for x in aggs], selected=out.selected,
+            verified=bool(got == want and got4 == want and psum == want[1]),
+            bytes_read=out.bytes_read, proj_bytes_read=pout.bytes_read,
+            column_bytes=out.column_bytes, groups=out.groups, pairs=len(agg_s),
+            aggregate_ms=[round(x * 1e3, 2) for x in agg_s],
+            project_sum_ms=[round(x * 1e3, 2) for x in proj_s],
+            four_scans_ms=[round(x * 1e3, 2) for x in four_s],
+            ratio_aggregate_over_project_sum=[round(r, 4) for r in ratios],
+            median_ratio=round(float(np.median(ratios)), 4),
+            median_ratio_vs_four_scans=round(float(np.median(
+                [x / y for x, y in zip(agg_s, four_s)])), 4),
+            column_GBps=round(out.column_bytes / float(np.median(agg_s)) / 1e9, 2))
+        _log(json.dumps(rows[label]))
+    return rows
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1 << 27)
@@ -191,6 +287,10 @@ def main(argv=None) -> int:
     ap.add_argument("--no-strings", dest="strings", action="store_false",
                     help="skip the utf8 / dictionary / date / timestamp file and rows")
     ap.add_argument("--string-rows", type=int, default=1 << 26)
+    ap.add_argument("--agg", action="store_true",
+                    help="add the aggregate rows: ArrowScan.aggregate alternated with "
+                         "scan_where(project=) + a torch reduction")
+    ap.add_argument("--agg-pairs", type=int, default=5)
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     import torch
@@ -297,6 +397,8 @@ def main(argv=None) -> int:
     try:
         for label, quals, proj in specs:
             run(path, fd, label, quals, proj, verify_np(quals, proj))
+        if a.agg:
+            res["agg"] = agg_rows(path, fd, a, col)
     finally:
         os.close(fd)
     if a.strings:
@@ -340,8 +442,10 @@ def main(argv=None) -> int:
         finally:
             os.close(sfd)
     base_rows = [res["columns"][lb] for lb, _, _ in specs]
-    res["arrow_scan_GBps"] = min(c["column_GBps"] for c in base_rows)
-    res["verified"] = all(c["verified"] for c in res["columns"].values())
+    if base_rows:
+        res["arrow_scan_GBps"] = min(c["column_GBps"] for c in base_rows)
+    res["verified"] = all(c["verified"] for c in res["columns"].values()) and \
+        all(r["verified"] for r in res.get("agg", {}).values())
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:

@@ -34,7 +34,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=1.0)
     ap.add_argument("--only", default="crc,scatter,verify,heap,lz4,snappy,filter",
-                    help="also: mvcc (snapshot check), par (LZ4 decoders by stream count)")
+                    help="also: mvcc (snapshot check), par (LZ4 decoders by stream count), "
+                         "agg (aggregate kernels next to column_filter_i64)")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     only = set(a.only.split(","))
@@ -178,11 +179,58 @@ def main(argv=None):
         log("column_filter_i64", timed(lambda: column_filter(v, -100, 100)), nv * 8)
         bm, cnt = column_filter(v, -100, 100)
         log("bitmap_to_indices", timed(lambda: bitmap_to_indices(bm, nv, cnt)), nv // 8 + cnt * 4)
+    if "agg" in only:
+        _agg_rows(n, dev, log, column_filter)
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:
             f.write(js)
     print(js)
+
+
+def _agg_rows(n, dev, log, column_filter):
+    """The aggregate kernels (colagg.hip: the launch over the column plus the
+    slab reduce) on one HBM-resident record batch, at 100 % and 10 %
+    selection; GB/s of the column bytes the query reads (values, and the
+    int32 keys of a grouped row), next to column_filter_i64 of the same run —
+    both stream a column once.  Grouped rows: uniform keys over G slots (the
+    null slot included), and one fully skewed row (every row the same key)."""
+    from nvme_strom_amd.ops import colagg as A
+    nv = n // 8
+    v = torch.randint(-1000, 1000, (nv,), dtype=torch.int64, device=dev)
+    f = torch.rand(nv, dtype=torch.float64, device=dev)
+    log("column_filter_i64", timed(lambda: column_filter(v, -100, 100)), nv * 8)
+    nwords = (nv + 63) // 64
+
+    def tab(t):
+        return torch.tensor([[t.data_ptr(), 0, nv, 0, 0]], dtype=torch.int64, device=dev)
+    tv, tf = tab(v), tab(f)
+    sels = {"100": torch.full((nwords,), -1, dtype=torch.int64, device=dev),
+            "10": column_filter(v, -100, 99)[0]}
+
+    def row(name, lay, t, key, nbytes):
+        block = A.alloc_block(lay, dev)
+        for tag, bm in sels.items():
+            slabs = torch.empty(A.slab_words(lay, 0, nwords), dtype=torch.int64, device=dev)
+
+            def go():
+                _, k = A.agg_launch(lay, 0, block, bm, nwords, t, key, slabs)
+                A.agg_reduce(lay, 0, block, slabs, k)
+            log(f"{name}_sel{tag}", timed(go), nbytes)
+    row("column_agg_i64_sum", A.Layout([A.Entry(A.SUM, "i8")]), tv, None, nv * 8)
+    row("column_agg_f64_sum_min_max", A.Layout([A.Entry(A.SUM | A.MIN | A.MAX, "f8")]), tf, None,
+        nv * 8)
+    for G in (3, 256, 4096):
+        k = torch.randint(0, G - 1, (nv,), dtype=torch.int32, device=dev)
+        row(f"column_agg_i64_sum_by{G}", A.Layout([A.Entry(A.SUM, "i8")], G, 1), tv, tab(k),
+            nv * 12)
+        if G == 256:
+            row(f"column_agg_f64_sum_min_max_by{G}",
+                A.Layout([A.Entry(A.SUM | A.MIN | A.MAX, "f8")], G, 1), tf, tab(k), nv * 12)
+        del k
+    k = torch.full((nv,), 7, dtype=torch.int32, device=dev)
+    row("column_agg_i64_sum_by256_skewed", A.Layout([A.Entry(A.SUM, "i8")], 256, 1), tv, tab(k),
+        nv * 12)
 
 
 def _mvcc_rows(n, dev, log):

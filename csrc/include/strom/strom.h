@@ -653,6 +653,54 @@ int strom_column_agg_many(const struct strom_agg_entry *e, uint32_t n, const uin
 int strom_column_agg_reduce_many(const struct strom_agg_entry *e, uint32_t n, uint32_t nslots,
                                  uint64_t nwords, void *stream);
 
+/* Hash join of a scan's foreign-key column with a dimension table
+ * (csrc/kernels/coljoin.hip; Arrow scans: the join= of ArrowScan.scan_where /
+ * aggregate).
+ *
+ * The table is STROM_JOIN_HDR_WORDS + 2 * capacity 64-bit words on the device,
+ * 16-byte aligned: the header, then capacity 16-byte slots of (key, payload in
+ * the low 32 bits), open addressing with linear probing from
+ * strom_join_hash(key) & (capacity - 1).  capacity is a power of two >= 2n and
+ * >= 64 (strom_join_capacity).  Every int64 is a legal key: a free slot holds
+ * STROM_JOIN_EMPTY, and that key itself is kept in the header.  The header's
+ * MAXDISP is the largest distance of an inserted key from its home slot: a
+ * probe looks at no more than MAXDISP + 1 slots.
+ *
+ * strom_join_build clears the table and inserts d_keys[0..n) with payload
+ * d_payload[i] (NULL: i, the build row).  A key met a second time is counted
+ * in DUPS and not inserted (which of the equal keys' payloads stays is not
+ * defined).
+ *
+ * strom_column_join walks a selection bitmap like strom_column_qual (batch
+ * b on words [word_base, ...), the last word bounded by nrows):
+ *   SEMI  d_dst[w] = d_src[w] & match      ANTI  d_dst[w] = d_src[w] & ~match
+ * over the rows that exist, where match = the row's fk is not null and is a key
+ * of the table (a null fk matches nothing: ANTI keeps it).  d_dst may be d_src.
+ * *d_count += popcount of the d_dst words.  type: the fk's storage, one of
+ * STROM_COL_I8/I16/I32/I64/U8/U16/U32/U64 widened to int64 (a U64 value >=
+ * 2^63 matches nothing); anything else is -EINVAL.  d_kout (SEMI only; may be
+ * NULL): a table of the same batches whose values point to int32 buffers of
+ * nrows elements; each selected matched row's payload is written at its row,
+ * no other element is touched. */
+#define STROM_JOIN_HDR_WORDS 8
+#define STROM_JOIN_EMPTY 0x8000000000000000ull
+#define STROM_JOIN_H_CAPACITY 0
+#define STROM_JOIN_H_NKEYS 1
+#define STROM_JOIN_H_MAXDISP 2
+#define STROM_JOIN_H_DUPS 3
+#define STROM_JOIN_H_HAS_EMPTY 4
+#define STROM_JOIN_H_EMPTY_PAYLOAD 5
+#define STROM_JOIN_SEMI 0
+#define STROM_JOIN_ANTI 1
+uint64_t strom_join_capacity(uint64_t n);
+uint64_t strom_join_hash(int64_t key);
+int strom_join_build(const int64_t *d_keys, const int32_t *d_payload, uint64_t n,
+                     uint64_t *d_table, uint64_t capacity, void *stream);
+int strom_column_join(int type, int how, const uint64_t *d_table, uint64_t capacity,
+                      const struct strom_filter_batch *d_fk, uint32_t nbatches, uint64_t nwords,
+                      const uint64_t *d_src, uint64_t *d_dst,
+                      const struct strom_filter_batch *d_kout, uint64_t *d_count, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

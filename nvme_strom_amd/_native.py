@@ -322,6 +322,13 @@ _SIGS = {
                                         C.c_void_p]),
     "strom_column_agg_reduce_many": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64,
                                                C.c_void_p]),
+    "strom_join_capacity": (C.c_uint64, [C.c_uint64]),
+    "strom_join_hash": (C.c_uint64, [C.c_int64]),
+    "strom_join_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                   C.c_void_p]),
+    "strom_column_join": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
+                                    C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
     "strom_io_info": (C.c_int, [C.c_void_p]),
     "strom_io_prof": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "strom_arrow_headers": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,

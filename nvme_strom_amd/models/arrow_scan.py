@@ -40,6 +40,7 @@ import torch
 
 from .. import api
 from ..ops import colagg as A
+from ..ops import coljoin as J
 from ..ops import decompress as D
 from ..ops.colfilter import BATCH_FIELDS, bitmap_to_rows, bitmap_to_rows_str
 from ..ops.colpred import (COL_CODE, QUAL_BATCH_FIELDS, Compiled, Pred, clauses, compile_pred,
@@ -54,6 +55,171 @@ from ..utils.arrow_ipc import (ArrowFile, Column, _Src, decode_values, dictionar
 _TORCH = {"i1": torch.int8, "u1": torch.uint8, "i2": torch.int16, "u2": torch.uint16,
           "i4": torch.int32, "u4": torch.uint32, "i8": torch.int64, "u8": torch.uint64,
           "f4": torch.float32, "f8": torch.float64}
+
+
+class JoinAttr:
+    """One attribute of a JoinTable (``dim["category"]``): what ``by=`` and
+    ``project=`` name to group by or gather the joined attribute."""
+
+    def __init__(self, table: "JoinTable", name: str):
+        self.table, self.name = table, name
+
+    @property
+    def values(self) -> list:
+        """The value of each code (None: the attribute was null)."""
+        return self.table._attrs[self.name][0]
+
+    @property
+    def codes(self) -> np.ndarray:
+        """The code of each build row (int32)."""
+        return self.table._attrs[self.name][1]
+
+    def __repr__(self) -> str:
+        return f"JoinAttr({self.name!r})"
+
+
+def _pylist(x) -> list:
+    if hasattr(x, "to_pylist"):
+        return x.to_pylist()
+    if isinstance(x, np.ndarray):
+        return x.tolist()
+    return list(x)
+
+
+class JoinTable:
+    """The build side of a join: a dimension table's unique integer key and
+    any number of attributes, one value per key.
+
+    ``keys``: an integer numpy or pyarrow array; null keys are dropped with
+    their attribute values (they never match).  ``attrs``: name -> strings,
+    integers or bools, factorized on the host into codes 0..m-1 in order of
+    first appearance; a null value is one ordinary code whose value is None.
+    ``device``: where the hash tables (csrc/kernels/coljoin.hip) are built —
+    one per attribute, its payload the attribute's code, and one whose
+    payload is the build row; None keeps the table on the host (the CPU
+    twins).  A key that appears twice raises ValueError after the build.  An
+    empty table is legal.  Built once, usable by any number of scans on its
+    device; ``close()`` frees it."""
+
+    def __init__(self, keys, attrs: Optional[dict] = None, device=None):
+        valid = None
+        if hasattr(keys, "to_numpy") and hasattr(keys, "null_count"):      # pyarrow
+            if hasattr(keys, "combine_chunks"):
+                keys = keys.combine_chunks()
+            if keys.null_count:
+                valid = np.asarray(keys.is_valid())
+                keys = keys.fill_null(0)
+            keys = keys.to_numpy(zero_copy_only=False)
+        keys = np.asarray(keys)
+        if keys.ndim != 1 or keys.dtype.kind not in "iu":
+            raise ValueError("JoinTable keys: a one-dimensional integer array")
+        if keys.dtype == np.uint64 and len(keys) and int(keys.max()) >= 1 << 63:
+            raise ValueError("JoinTable keys: values >= 2^63 are not int64 keys")
+        nall = len(keys)
+        keys = keys.astype(np.int64)
+        self.keys = keys if valid is None else keys[valid]
+        self._attrs: Dict[str, tuple] = {}
+        for name, vals in (attrs or {}).items():
+            vals = _pylist(vals)
+            if len(vals) != nall:
+                raise ValueError(f"attribute {name}: {len(vals)} values for {nall} keys")
+            if valid is not None:
+                vals = [v for v, ok in zip(vals, valid) if ok]
+            code: Dict[object, int] = {}
+            # bools and integers are different attribute values (True != 1)
+            codes = np.fromiter((code.setdefault((type(v) is bool, v), len(code)) for v in vals),
+                                np.int32, len(vals))
+            self._attrs[str(name)] = ([v for _, v in code], codes)
+        self.device = torch.device(device) if device is not None else None
+        self._host: Optional[J.HostTable] = None
+        self._dev: Dict[Optional[str], J.DeviceTable] = {}
+        self._dkeys = None
+        if self.device is not None:
+            # every table now, so that no scan builds (and syncs for) one
+            for name in [None] + list(self._attrs):
+                self._device_table(name)
+            dups = int(self._dev[None].header()[J.H_DUPS])
+        else:
+            dups = self.host().dups
+        if dups:
+            self.close()
+            raise ValueError(f"JoinTable: {dups} duplicate key(s): the dimension's key must be "
+                             "unique")
+
+    def __len__(self) -> int:
+        return len(self.keys)
+
+    def __getitem__(self, name: str) -> JoinAttr:
+        if name not in self._attrs:
+            raise ValueError(f"JoinTable has no attribute {name!r}")
+        return JoinAttr(self, name)
+
+    def host(self) -> J.HostTable:
+        """The numpy twin's table (payload: the build row)."""
+        if self._host is None:
+            self._host = J.host_build(self.keys)
+        return self._host
+
+    def _device_table(self, attr: Optional[str]) -> J.DeviceTable:
+        if self.device is None:
+            raise ValueError("JoinTable was built without a device")
+        if attr not in self._dev:
+            if self._dkeys is None:
+                self._dkeys = torch.from_numpy(self.keys).to(self.device)
+            pay = None
+            if attr is not None:
+                pay = torch.from_numpy(self._attrs[attr][1]).to(self.device)
+            with torch.cuda.device(self.device):
+                self._dev[attr] = J.build(self._dkeys, pay)
+                self._dev[attr].keep = pay
+                # the scans probe on their own streams
+                torch.cuda.current_stream(self.device).synchronize()
+        return self._dev[attr]
+
+    def close(self) -> None:
+        self._dev = {}
+        self._dkeys = None
+
+
+class Join:
+    """``join=Join("fk", dim, how="semi")``: keep the rows whose ``fk`` is a
+    key of ``dim`` (``how="anti"``: the rows whose ``fk`` is not; a null fk
+    matches nothing, so the anti-join keeps it, as pyarrow's "left anti")."""
+
+    def __init__(self, col: str, table: JoinTable, how: str = "semi"):
+        if how not in J.HOW:
+            raise ValueError(f"join how={how!r}: one of {sorted(J.HOW)}")
+        if not isinstance(table, JoinTable):
+            raise TypeError("Join: the build side is a JoinTable")
+        self.col, self.table, self.how = str(col), table, how
+
+
+def _check_join(meta: ArrowFile, join, attr) -> Optional[Join]:
+    """Validate ``join=`` and the JoinAttr of ``by=`` / ``project=`` (or
+    None) against the schema."""
+    if isinstance(join, (list, tuple)):
+        raise NotImplementedError("one join per scan (a list of joins is not supported)")
+    if join is None:
+        if attr is not None:
+            raise ValueError(f"{attr!r} needs join= with its JoinTable")
+        return None
+    if not isinstance(join, Join):
+        raise TypeError("join=: a Join")
+    schema = {c.name: c for c in meta.schema}
+    if join.col not in schema:
+        raise ValueError(f"no column {join.col!r}")
+    c = schema[join.col]
+    if c.dictionary is not None or c.kind != "int" or c.storage not in J.FK_CODE:
+        kind = "dictionary-encoded" if c.dictionary is not None else c.kind
+        raise NotImplementedError(f"join on {join.col}: {kind} columns are not joined "
+                                  "(integer columns are)")
+    if attr is not None:
+        if attr.table is not join.table:
+            raise ValueError(f"{attr!r} belongs to another JoinTable than the one in join=")
+        if join.how == "anti":
+            raise ValueError(f"{attr!r} with how='anti': the rows an anti-join keeps matched "
+                             "nothing")
+    return join
 
 
 @dataclass
@@ -71,6 +237,16 @@ class ScanOut:
     dictionary: object = None               # its decoded dictionary when dictionary-encoded
     offsets: Optional[torch.Tensor] = None  # utf8/binary projection: int64[selected + 1]
                                             # into ``values`` (the characters, uint8)
+
+
+@dataclass
+class _JoinRun:
+    """A scan's join as _compute sees it."""
+    col: int                      # plan column of the foreign key
+    code: int                     # its STROM_COL_* storage type
+    how: str
+    dev: J.DeviceTable
+    attr: Optional[str] = None    # attribute whose codes the probe writes
 
 
 @dataclass
@@ -169,6 +345,7 @@ class _Slot:
     pending: object = None                # (CopyResult, landed ids, group)
     keep: List[torch.Tensor] = field(default_factory=list)
     pin: Optional[torch.Tensor] = None     # pinned arena for the group's tables
+    keybuf: Optional[torch.Tensor] = None  # int32 per row: the joined attribute's code
     pin_off: int = 0
 
 
@@ -717,6 +894,7 @@ class ArrowScan:
                     tabs[col] = self._upload(s, t)
                     s.keep.append(tabs[col])
                 return tabs[col]
+            jn = state.get("join")
             # the CNF qualifier list: clause 0 writes the bitmap (its
             # predicates ORed in place), a later single-predicate clause ANDs
             # into it, a later OR-clause collects in the scratch bitmap and
@@ -724,7 +902,7 @@ class ArrowScan:
             # last launch's count is the selection's
             for ci, clause in enumerate(spec):
                 for j, (col, cq) in enumerate(clause):
-                    last = ci == len(spec) - 1 and j == len(clause) - 1
+                    last = jn is None and ci == len(spec) - 1 and j == len(clause) - 1
                     cnt = s.count if last else s.junk
                     if ci == 0:
                         qual_batched(cq, table(col), g.words, s.bitmap, cnt, stream=cs,
@@ -746,9 +924,36 @@ class ArrowScan:
                     g.ones = _all_rows_bitmap(g.table[:, 2])
                 bitmap = self._upload(s, g.ones)
                 s.keep.append(bitmap)
+            d_kout = None
+            kout_ptr = 0
+            if jn is not None:
+                # the probe, the list's last launch (and_dst semantics, its
+                # count is the selection's): the fk's batch table and, when an
+                # attribute is wanted, the table of the slot's key buffer —
+                # batch b's codes at row word_base * 64 — go up in one copy
+                n = len(g.table)
+                fk5 = (tabs_np[jn.col] if jn.col in tabs_np else
+                       self._pointers(g, jn.col, base, dec_base))[:, :BATCH_FIELDS]
+                both = [fk5]
+                if jn.attr is not None:
+                    if s.keybuf is None or s.keybuf.numel() < s.bitmap.numel() * 64:
+                        s.keybuf = torch.empty(s.bitmap.numel() * 64, dtype=torch.int32,
+                                               device=self.device)
+                    k5 = fk5.copy()
+                    k5[:, 0] = s.keybuf.data_ptr() + g.table[:, 3] * 256
+                    k5[:, 1] = 0
+                    both.append(k5)
+                d_j = self._upload(s, np.stack(both))
+                s.keep.append(d_j)
+                if jn.attr is not None:
+                    d_kout = d_j[1]
+                    kout_ptr = d_kout.data_ptr()
+                J.probe(jn.dev, jn.code, d_j[0], g.words, bitmap, s.bitmap, s.count,
+                        how=J.HOW[jn.how], key_out=d_kout, stream=cs)
+                bitmap = s.bitmap
             state["marks"].append((k, "quals_queued", time.perf_counter()))
             # emit tables: the strom_filter_batch prefix of the qual tables
-            any_col = spec[0][0][0] if spec else 0
+            any_col = spec[0][0][0] if spec else (jn.col if jn is not None else 0)
             d_rows = table(any_col)[:, :BATCH_FIELDS].contiguous()
             agg = state.get("agg")
             if agg is not None:
@@ -779,10 +984,12 @@ class ArrowScan:
                     args[e].slabs = o
                     o += 8 * sw[e]
                 A.agg_many(lay, args, state["block"], bitmap, g.words,
-                           at[agg.key_col] if agg.key_col is not None else 0, n, stream=cs)
+                           at[agg.key_col] if agg.key_col is not None else kout_ptr, n, stream=cs)
             pstr = state.get("pchars") is not None
             d_proj = None
-            if proj is not None:
+            if state.get("pattr"):
+                d_proj = d_kout                  # the joined attribute's codes
+            elif proj is not None:
                 d_proj = table(proj) if pstr else table(proj)[:, :BATCH_FIELDS].contiguous()
             s.keep += [d_rows] + ([d_proj] if d_proj is not None else [])
         # decode + filter of successive groups overlap on their slots'
@@ -833,8 +1040,20 @@ class ArrowScan:
             self._compiled[key] = compile_pred(p, col, dic)
         return self._compiled[key]
 
-    def scan_where(self, quals, project: Optional[str] = None,
-                   batches: Optional[Tuple[int, int]] = None) -> ScanOut:
+    def _join_run(self, join: Join, names: List[str], attr: Optional[JoinAttr]) -> _JoinRun:
+        td = join.table.device
+        # "cuda" and "cuda:<current device>" are the same place
+        idx = lambda d: d.index if d.index is not None else torch.cuda.current_device()
+        if td is None or td.type != self.device.type or (td != self.device and
+                                                          idx(td) != idx(self.device)):
+            raise ValueError(f"JoinTable on {td}, scan on {self.device}")
+        col = self.meta.schema[self.meta.column_index(join.col)]
+        name = attr.name if attr is not None else None
+        return _JoinRun(names.index(join.col), J.FK_CODE[col.storage], join.how,
+                        join.table._device_table(name), name)
+
+    def scan_where(self, quals, project=None, batches: Optional[Tuple[int, int]] = None,
+                   join: Optional[Join] = None) -> ScanOut:
         """Row ids (int64, file order) of the rows every qualifier selects —
         a PG-Strom qualifier list.  ``quals`` items: ``(name, lo, hi)``
         ranges, ``(name, op, value)`` / ``P(name) <op> value`` predicates,
@@ -850,11 +1069,22 @@ class ArrowScan:
         nulls, are gathered for the selected rows while their ids are
         written.  ``batches=(b0, b1)``
         scans only record batches [b0, b1) (row ids stay file-global:
-        parallel/scan.py splits a file over ranks this way)."""
-        cl = clauses(quals)
+        parallel/scan.py splits a file over ranks this way).
+        ``join=Join(fk, dim, how)`` keeps the rows whose ``fk`` is (semi) or
+        is not (anti) a key of the JoinTable ``dim``: a hash probe
+        (csrc/kernels/coljoin.hip) on the slot's stream after the qualifier
+        list, which may then be empty.  ``project=dim[attr]`` gathers the
+        joined attribute's code per selected row (``ScanOut.dictionary``
+        holds the codes' values)."""
+        pattr = project if isinstance(project, JoinAttr) else None
+        join = _check_join(self.meta, join, pattr)
+        if pattr is not None:
+            project = None
+        cl = clauses(quals) if (quals or join is None) else []
         t0 = time.perf_counter()
         names: List[str] = []
-        for n in [p.col for c in cl for p in c] + ([project] if project else []):
+        for n in [p.col for c in cl for p in c] + ([join.col] if join else []) + \
+                ([project] if project else []):
             if n not in names:
                 names.append(n)
         nb = self.meta.nbatches
@@ -892,6 +1122,9 @@ class ArrowScan:
             if any(bool(g.has_valid[pcol]) for g in groups):
                 pvalid = torch.empty(max(nrows, 1), dtype=torch.uint8, device=self.device)
         pdict = self.dictionary(project) if project and pmeta.dictionary is not None else None
+        if pattr is not None:
+            pout = torch.empty(max(nrows, 1), dtype=torch.int32, device=self.device)
+            pdict = pattr.values
         if not groups or nrows == 0:
             return ScanOut(nrows, 0, out[:0], {"total_s": time.perf_counter() - t0},
                            values=pout[:0] if pout is not None else
@@ -907,6 +1140,9 @@ class ArrowScan:
         state = dict(out=out, cursor=z(), count=z(), err=z(), wait_s=0.0, bytes_read=0,
                      column_bytes=0, pout=pout, pvalid=pvalid, pchars=pchars, poff=poff,
                      ccursor=z(), owidth=8 if pstrings and pmeta.large else 4, marks=[])
+        if join is not None:
+            state["join"] = self._join_run(join, names, pattr)
+            state["pattr"] = pattr is not None
         t_alloc = time.perf_counter()
         # depth nslots - 1 of reads ahead of the group being computed
         ahead = max(1, min(self.nslots, len(self._slots)) - 1)
@@ -947,8 +1183,8 @@ class ArrowScan:
                        valid=pvalid[:count] if pvalid is not None else None,
                        column=pmeta, dictionary=pdict, offsets=offsets)
 
-    def aggregate(self, quals, aggs, by: Optional[str] = None,
-                  batches: Optional[Tuple[int, int]] = None) -> "AggOut":
+    def aggregate(self, quals, aggs, by=None, batches: Optional[Tuple[int, int]] = None,
+                  join: Optional[Join] = None) -> "AggOut":
         """``SELECT by, aggs... WHERE quals GROUP BY by`` in one pass over
         the file: the qualifier, aggregated and key columns are read and
         decoded once per group, the qualifier kernels leave the selection
@@ -964,12 +1200,20 @@ class ArrowScan:
         bits, float sums are float64; NaN propagates into a sum and is
         ignored by min / max; nulls are skipped.  ``by``: a
         dictionary-encoded, bool or 8-bit integer column (null keys form a
-        group of their own, key None).  See AggOut."""
+        group of their own, key None).  ``join=`` as in scan_where: only the
+        joined rows are aggregated, and ``by=dim[attr]`` groups them by an
+        attribute of the JoinTable — the probe writes each row's attribute
+        code into the slot's key buffer and the aggregate kernels take it as
+        their key column.  See AggOut."""
         t0 = time.perf_counter()
+        battr = by if isinstance(by, JoinAttr) else None
+        join = _check_join(self.meta, join, battr)
+        if battr is not None:
+            by = None
         cl = clauses(quals) if quals else []
-        agg = _agg_spec(self.meta, aggs, by, self.dictionary)
+        agg = _agg_spec(self.meta, aggs, by, self.dictionary, battr)
         names: List[str] = []
-        for n in [p.col for c in cl for p in c] + agg.names:
+        for n in [p.col for c in cl for p in c] + ([join.col] if join else []) + agg.names:
             if n not in names:
                 names.append(n)
         nb = self.meta.nbatches
@@ -994,6 +1238,7 @@ class ArrowScan:
             return _agg_out(agg, A.new_block(agg.layout), nrows,
                             {"total_s": time.perf_counter() - t0})
         agg.entry_cols = [None if n is None else names.index(n) for n in agg.entry_names]
+        # by=dim[attr]: no file column, the key is the probe's code buffer
         agg.key_col = names.index(by) if by is not None else None
         self._ensure_slots(groups)
         if getattr(self, "emit_stream", None) is None:
@@ -1004,6 +1249,8 @@ class ArrowScan:
             block = A.alloc_block(agg.layout, self.device, stream=self.emit_stream)
         state = dict(agg=agg, block=block, count=z(), err=z(), wait_s=0.0, bytes_read=0,
                      column_bytes=0, marks=[])
+        if join is not None:
+            state["join"] = self._join_run(join, names, battr)
         # the aggregate launches (slot streams) count malformed keys in the
         # block: they must see it initialised
         ready = torch.cuda.Event()
@@ -1034,12 +1281,12 @@ class ArrowScan:
                         bytes_read=state["bytes_read"], column_bytes=state["column_bytes"],
                         groups=len(groups))
 
-    def host_aggregate(self, quals, aggs, by: Optional[str] = None,
-                       batches: Optional[Tuple[int, int]] = None) -> "AggOut":
+    def host_aggregate(self, quals, aggs, by=None, batches: Optional[Tuple[int, int]] = None,
+                       join: Optional[Join] = None) -> "AggOut":
         """The same query on the CPU (host_scan_where's path plus the
         aggregate kernels' numpy twin, ops/colagg.py)."""
         return host_aggregate(self.path, quals, aggs, by, batches, meta=self.meta,
-                              dicts=self._dicts)
+                              dicts=self._dicts, join=join)
 
     def scan(self, name: str, lo, hi) -> ScanOut:
         """Row ids (int64, file order) of ``lo <= column <= hi`` (nulls never
@@ -1049,12 +1296,13 @@ class ArrowScan:
     # the pre-pipeline name
     filter = scan
 
-    def host_scan_where(self, quals, project: Optional[str] = None,
-                        batches: Optional[Tuple[int, int]] = None) -> "HostScanOut":
+    def host_scan_where(self, quals, project=None, batches: Optional[Tuple[int, int]] = None,
+                        join: Optional[Join] = None) -> "HostScanOut":
         """The same query on the CPU (buffers read with pread, decoded by
-        the decoders' host twins, predicates by colpred's numpy twin)."""
+        the decoders' host twins, predicates by colpred's numpy twin, the
+        join by coljoin's)."""
         return host_scan_where(self.path, quals, project, batches, meta=self.meta,
-                               dicts=self._dicts)
+                               dicts=self._dicts, join=join)
 
     def _free_slots(self) -> None:
         if self._slots:
@@ -1078,18 +1326,32 @@ class HostScanOut:
     indices: np.ndarray                # int64 global row ids
     values: object = None              # projected values (numpy; strings: list of bytes)
     valid: Optional[np.ndarray] = None
+    dictionary: object = None          # project=dim[attr]: the value of each code
 
 
-def host_scan_where(path: str, quals, project: Optional[str] = None,
+def _host_join(join: Join, v, ok, m: np.ndarray):
+    """(rows of ``m`` the join keeps, build row per row) for one batch's
+    foreign keys ``v`` / validity ``ok``."""
+    keys, can = J.widen(np.asarray(v))
+    act = m & can & (np.ones(len(m), bool) if ok is None else np.asarray(ok, bool))
+    match, row = J.host_lookup(join.table.host(), keys, act)
+    return (m & ~match if join.how == "anti" else m & match), row
+
+
+def host_scan_where(path: str, quals, project=None,
                     batches: Optional[Tuple[int, int]] = None, meta: Optional[ArrowFile] = None,
-                    dicts: Optional[dict] = None) -> HostScanOut:
+                    dicts: Optional[dict] = None, join: Optional[Join] = None) -> HostScanOut:
     """ArrowScan.scan_where on the CPU: the same metadata, the same
     compiled predicates (ops/colpred.py), evaluated by the kernel's numpy
     twin over buffers decoded by the GPU decoders' host twins.  The
     reference point for the GPU path and a scan for machines without one."""
     meta = meta if meta is not None else read_metadata(path)
     dicts = dicts if dicts is not None else {}
-    cl = clauses(quals)
+    pattr = project if isinstance(project, JoinAttr) else None
+    join = _check_join(meta, join, pattr)
+    if pattr is not None:
+        project = None
+    cl = clauses(quals) if (quals or join is None) else []
     schema = {c.name: (i, c) for i, c in enumerate(meta.schema)}
 
     def dictionary(name):
@@ -1105,7 +1367,8 @@ def host_scan_where(path: str, quals, project: Optional[str] = None,
                 p.op not in ("is_null", "is_valid") else None
             row.append((p.col, compile_pred(p, col, dic)))
         comp.append(row)
-    names = sorted({n for c in comp for n, _ in c} | ({project} if project else set()))
+    names = sorted({n for c in comp for n, _ in c} | ({project} if project else set()) |
+                   ({join.col} if join else set()))
     nb = meta.nbatches
     b0, b1 = (0, nb) if batches is None else (max(0, batches[0]), min(nb, batches[1]))
     base = np.concatenate([[0], np.cumsum(meta.rows)]).astype(np.int64)
@@ -1133,8 +1396,14 @@ def host_scan_where(path: str, quals, project: Optional[str] = None,
                     v, ok = data[name]
                     cm |= evaluate(cq, v, ok, n)
                 m &= cm
+            if join is not None:
+                m, jrow = _host_join(join, *data[join.col], m)
             sel = np.flatnonzero(m)
             ids.append(sel + base[bi])
+            if pattr is not None:
+                vals.append(pattr.codes[jrow[sel]] if len(pattr.codes) else
+                            np.zeros(0, np.int32))
+                valid.append(np.ones(len(sel), bool))
             if project:
                 v, ok = data[project]
                 if isinstance(v, tuple):
@@ -1147,11 +1416,13 @@ def host_scan_where(path: str, quals, project: Optional[str] = None,
         src.close()
     out = HostScanOut(int(base[b1] - base[b0]) if b1 > b0 else 0,
                       np.concatenate(ids) if ids else np.zeros(0, np.int64))
-    if project:
+    if pattr is not None:
+        out.dictionary = pattr.values
+    if project or pattr is not None:
         if vals and isinstance(vals[0], list):
             out.values = [x for v in vals for x in v]
         else:
-            out.values = np.concatenate(vals) if vals else np.zeros(0)
+            out.values = np.concatenate(vals) if vals else np.zeros(0, np.int32 if pattr else None)
         vv = np.concatenate(valid) if valid else np.zeros(0, bool)
         out.valid = None if vv.all() else vv
     return out
@@ -1187,9 +1458,11 @@ class _AggSpec:
     entry_cols: Optional[List[Optional[int]]] = None    # plan column of each entry (GPU)
     key_col: Optional[int] = None
     slab_words: Dict[int, List[int]] = field(default_factory=dict)   # by group words
+    join_attr: bool = False                 # ``by`` names a JoinTable attribute
 
 
-def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary) -> _AggSpec:
+def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary,
+              jattr: Optional[JoinAttr] = None) -> _AggSpec:
     """Validate ``aggs`` / ``by`` against the schema and lay the accumulator
     block out: entry 0 counts the selected rows per slot, then one entry per
     aggregated column with COUNT and whatever of SUM / MIN / MAX is asked."""
@@ -1246,6 +1519,11 @@ def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary) -> _AggSpec:
                 f"GROUP BY {by}: {k.kind} keys (dictionary-encoded, bool and 8-bit integer "
                 "columns are grouped on the GPU)")
         nslots = len(keyvals) + 1
+    if jattr is not None:
+        # the key column is the probe's int32 code buffer; every selected row
+        # matched, so the null slot stays empty (the kernels want two slots)
+        keyvals, key_code = list(jattr.values), COL_CODE["i4"]
+        nslots = max(len(keyvals), 1) + 1
     entries = [A.Entry(A.COUNT | A.ALL)]
     entry_names: List[Optional[str]] = [None]
     for col, o in ops.items():
@@ -1254,8 +1532,9 @@ def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary) -> _AggSpec:
     names = [n for n in entry_names[1:]]
     if by is not None and by not in names:
         names.append(by)
-    return _AggSpec(aggs, by, A.Layout(entries, nslots, key_code), entry_names, names,
-                    {n: schema[n] for n in names}, keyvals)
+    return _AggSpec(aggs, by if jattr is None else jattr.name,
+                    A.Layout(entries, nslots, key_code), entry_names, names,
+                    {n: schema[n] for n in names}, keyvals, join_attr=jattr is not None)
 
 
 @dataclass
@@ -1296,8 +1575,8 @@ class AggOut:
         counts and sums add, min and max combine."""
         a, b = self._spec, other._spec
         if a.aggs != b.aggs or a.by != b.by or a.layout.nslots != b.layout.nslots or \
-                a.keyvals != b.keyvals:
-            raise ValueError("merge: different aggregates, key or dictionary")
+                a.keyvals != b.keyvals or a.join_attr != b.join_attr:
+            raise ValueError("merge: different aggregates, key, dictionary or join attribute")
         secs = {"total_s": self.seconds.get("total_s", 0.0) + other.seconds.get("total_s", 0.0)}
         return _agg_out(a, A.merge_blocks(a.layout, self._block, other._block),
                         self.rows + other.rows, secs,
@@ -1346,9 +1625,9 @@ def _agg_out(spec: _AggSpec, block: np.ndarray, rows: int, seconds: Dict[str, fl
                   valid, columns, seconds, bytes_read, column_bytes, groups, spec, block)
 
 
-def host_aggregate(path: str, quals, aggs, by: Optional[str] = None,
+def host_aggregate(path: str, quals, aggs, by=None,
                    batches: Optional[Tuple[int, int]] = None, meta: Optional[ArrowFile] = None,
-                   dicts: Optional[dict] = None) -> AggOut:
+                   dicts: Optional[dict] = None, join: Optional[Join] = None) -> AggOut:
     """ArrowScan.aggregate on the CPU: buffers read with pread and decoded
     by the decoders' host twins, the qualifiers by colpred's numpy twin, the
     aggregates by colagg's.  The reference point for the GPU path and the
@@ -1363,7 +1642,11 @@ def host_aggregate(path: str, quals, aggs, by: Optional[str] = None,
         if name not in dicts:
             dicts[name] = dictionary_values(meta, schema[name][1], path)
         return dicts[name]
-    spec = _agg_spec(meta, aggs, by, dictionary)
+    battr = by if isinstance(by, JoinAttr) else None
+    join = _check_join(meta, join, battr)
+    if battr is not None:
+        by = None
+    spec = _agg_spec(meta, aggs, by, dictionary, battr)
     comp = []
     for c in cl:
         row = []
@@ -1375,7 +1658,8 @@ def host_aggregate(path: str, quals, aggs, by: Optional[str] = None,
                 p.op not in ("is_null", "is_valid") else None
             row.append((p.col, compile_pred(p, col, dic)))
         comp.append(row)
-    names = sorted({n for c in comp for n, _ in c} | set(spec.names))
+    names = sorted({n for c in comp for n, _ in c} | set(spec.names) |
+                   ({join.col} if join else set()))
     nb = meta.nbatches
     b0, b1 = (0, nb) if batches is None else (max(0, batches[0]), min(nb, batches[1]))
     lay = spec.layout
@@ -1391,8 +1675,9 @@ def host_aggregate(path: str, quals, aggs, by: Optional[str] = None,
                 ch = b.columns[ci]
                 vraw = read_buffer(src, ch.validity, b.codec) if ch.null_count else b""
                 ok = validity_bits(vraw, ch.length)
-                if not any(n == q for c in comp for q, _ in c) and \
-                        n != by and lay.entries[spec.entry_names.index(n)].dtype is None:
+                if not any(n == q for c in comp for q, _ in c) and n != by and \
+                        not (join and n == join.col) and \
+                        lay.entries[spec.entry_names.index(n)].dtype is None:
                     data[n] = (None, ok)          # counted only: its validity is enough
                     continue
                 d = read_buffer(src, ch.data, b.codec)
@@ -1411,6 +1696,11 @@ def host_aggregate(path: str, quals, aggs, by: Optional[str] = None,
                     cm |= evaluate(cq, v, ok, n)
                 m &= cm
             key = None
+            if join is not None:
+                m, jrow = _host_join(join, *data[join.col], m)
+                if battr is not None:
+                    key = (np.where(m, battr.codes[jrow] if len(battr.codes) else 0, 0)
+                           .astype(np.int32), None)
             if by is not None:
                 kv, kok = data[by]
                 kv = np.asarray(kv)

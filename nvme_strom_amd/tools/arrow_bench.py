@@ -36,6 +36,12 @@ whose time on the memory-mapped file is ``cpu_ms``.
 count(*), sum(id), min(x), max(x) under the ``val`` and ``x`` ranges, alternated
 with ``scan_where(project="id")`` + a torch sum, and against four such scans.
 
+``--join`` adds the join rows (``join_rows``): a scan whose last predicate
+is a semi-join of ``val`` with a 4,096-key dimension alternated with the same
+scan under ``P("val").isin(the same keys)``, and ``aggregate(join=,
+by=dim[attr])`` against two projection scans plus a torch searchsorted /
+gather / index_add.
+
 ``python -m nvme_strom_amd.tools.arrow_bench --out gpurun_out/arrow.json``
 """
 from __future__ import annotations
@@ -268,6 +274,137 @@ def agg_rows(path: str, fd: int, a, col) -> dict:
     return rows
 
 
+def join_rows(path: str, fd: int, a, col) -> dict:
+    """Scan row: ``scan_where([x range], join=Join("val", dim))`` alternated
+    with ``scan_where([x range, P("val").isin(keys)])`` for the same 4,096
+    keys — the largest list the qualifier kernels hold; both read and decode
+    ``x`` and ``val``, only the last launch differs.  Query row:
+    ``aggregate([x range], [count(*), sum(id)], by=dim["cat"], join=)`` over
+    a 131,072-key dimension of 64 categories against what it takes without
+    the join: ``scan_where(project="val")`` and ``scan_where(project="id")``,
+    then searchsorted, gather and index_add in torch.  ``--join-pairs``
+    alternated runs, the order flipped every pair, the file evicted before
+    every run; ratios are medians over the pairs."""
+    import torch
+
+    import nvme_strom_amd as S
+    from nvme_strom_amd.models.arrow_scan import ArrowScan, Join, JoinTable
+    from nvme_strom_amd.ops.colpred import P
+    rng = np.random.default_rng(17)
+    quals = [("x", 0.25, 0.75)]
+    all_keys = rng.choice(1_000_000, 4096, replace=False).astype(np.int64)
+    bkeys = np.sort(rng.choice(1_000_000, 131_072, replace=False)).astype(np.int64)
+    bcats = rng.integers(0, 64, len(bkeys))
+    big = JoinTable(bkeys, attrs={"cat": bcats}, device="cuda")
+    ncat = len(big["cat"].values)
+    d_bkeys = torch.from_numpy(bkeys).cuda()
+    d_bcodes = torch.from_numpy(big["cat"].codes.astype(np.int64)).cuda()
+    sc = ArrowScan(path, "cuda", slot_bytes=a.slot_mib << 20, nslots=a.nslots or None,
+                   chunk_sz=(a.chunk_kib << 10) or None)
+
+    def timed(fn):
+        S.evict_file(fd)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t, out
+
+    def t_join():
+        return timed(lambda: sc.scan_where(quals, join=Join("val", dim)))
+
+    def t_isin():
+        return timed(lambda: sc.scan_where(quals + [P("val").isin(keys.tolist())]))
+
+    aggs = [("count", None), ("sum", "id")]
+
+    def t_agg():
+        return timed(lambda: sc.aggregate(quals, aggs, by=big["cat"], join=Join("val", big)))
+
+    def two_scans():
+        fk = sc.scan_where(quals, project="val")
+        ids = sc.scan_where(quals, project="id")
+        pos = torch.searchsorted(d_bkeys, fk.values).clamp_(max=len(bkeys) - 1)
+        hit = d_bkeys[pos] == fk.values
+        codes = d_bcodes[pos[hit]]
+        cnt = torch.bincount(codes, minlength=ncat)
+        sm = torch.zeros(ncat, dtype=torch.int64, device="cuda").index_add_(0, codes,
+                                                                            ids.values[hit])
+        return cnt.cpu().numpy(), sm.cpu().numpy(), fk.bytes_read + ids.bytes_read
+    dim = None
+    try:
+        # cold runs: plans, slots, code objects.  The isin list is as long as
+        # the qualifier kernel's LDS staging takes on this device
+        for nk in (4096, 4064, 3072):
+            keys = np.sort(all_keys[:nk])
+            try:
+                t_isin()
+                break
+            except RuntimeError as e:
+                _log(f"isin of {nk} keys refused: {e}")
+        dim = JoinTable(keys, device="cuda")
+        t_join(), t_agg(), timed(two_scans)
+        join_s, isin_s, agg_s, two_s = [], [], [], []
+        for k in range(max(1, a.join_pairs)):
+            for what in (("join", "isin") if k % 2 == 0 else ("isin", "join")):
+                if what == "join":
+                    dt, jout = t_join()
+                    join_s.append(dt)
+                else:
+                    dt, iout = t_isin()
+                    isin_s.append(dt)
+            for what in (("agg", "two") if k % 2 == 0 else ("two", "agg")):
+                if what == "agg":
+                    dt, aout = t_agg()
+                    agg_s.append(dt)
+                else:
+                    dt, (tcnt, tsum, tbytes) = timed(two_scans)
+                    two_s.append(dt)
+            _log(f"join pair {k}: join {join_s[-1] * 1e3:.1f} ms, isin {isin_s[-1] * 1e3:.1f} ms; "
+                 f"aggregate {agg_s[-1] * 1e3:.1f} ms, two scans + torch {two_s[-1] * 1e3:.1f} ms")
+    finally:
+        sc.close()
+        if dim is not None:
+            dim.close()
+        big.close()
+    xv, xok = col("x")
+    m = (xv >= 0.25) & (xv <= 0.75)
+    if xok is not None:
+        m &= xok
+    val = col("val")[0]
+    ref = np.flatnonzero(m & np.isin(val, keys))
+    ok_scan = bool(np.array_equal(jout.indices.cpu().numpy(), ref) and
+                   np.array_equal(iout.indices.cpu().numpy(), ref))
+    mb = m & np.isin(val, bkeys)
+    code = big["cat"].codes[np.searchsorted(bkeys, val[mb])]
+    want_cnt = np.bincount(code, minlength=ncat)
+    want_sum = np.zeros(ncat, np.int64)
+    np.add.at(want_sum, code, col("id")[0][mb])
+    order = [big["cat"].values.index(kv) for kv in aout.keys]
+    ok_agg = bool(np.array_equal(aout.count_all, want_cnt[order]) and
+                  np.array_equal(aout.get("sum", "id")[0], want_sum[order]) and
+                  np.array_equal(tcnt, want_cnt) and np.array_equal(tsum, want_sum))
+    r1 = [x / y for x, y in zip(join_s, isin_s)]
+    r2 = [x / y for x, y in zip(agg_s, two_s)]
+    rows = dict(
+        scan=dict(quals=[repr(q) for q in quals], keys=len(keys), selected=jout.selected,
+                  verified=ok_scan, bytes_read=jout.bytes_read, isin_bytes_read=iout.bytes_read,
+                  groups=jout.groups, pairs=len(r1),
+                  join_ms=[round(x * 1e3, 2) for x in join_s],
+                  isin_ms=[round(x * 1e3, 2) for x in isin_s],
+                  ratio_join_over_isin=[round(r, 4) for r in r1],
+                  median_ratio=round(float(np.median(r1)), 4),
+                  min_ratio=round(min(r1), 4), max_ratio=round(max(r1), 4)),
+        query=dict(aggs=[list(x) for x in aggs], keys=len(bkeys), categories=ncat,
+                   selected=aout.selected, verified=ok_agg, bytes_read=aout.bytes_read,
+                   two_scans_bytes_read=int(tbytes), pairs=len(r2),
+                   aggregate_ms=[round(x * 1e3, 2) for x in agg_s],
+                   two_scans_torch_ms=[round(x * 1e3, 2) for x in two_s],
+                   median_ratio=round(float(np.median(r2)), 4),
+                   min_ratio=round(min(r2), 4), max_ratio=round(max(r2), 4)))
+    _log(json.dumps(rows))
+    return rows
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1 << 27)
@@ -291,6 +428,10 @@ def main(argv=None) -> int:
                     help="add the aggregate rows: ArrowScan.aggregate alternated with "
                          "scan_where(project=) + a torch reduction")
     ap.add_argument("--agg-pairs", type=int, default=5)
+    ap.add_argument("--join", action="store_true",
+                    help="add the join rows: a semi-join scan alternated with the same scan "
+                         "under isin(), and aggregate(join=, by=) against two projection scans")
+    ap.add_argument("--join-pairs", type=int, default=15)
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     import torch
@@ -399,6 +540,8 @@ def main(argv=None) -> int:
             run(path, fd, label, quals, proj, verify_np(quals, proj))
         if a.agg:
             res["agg"] = agg_rows(path, fd, a, col)
+        if a.join:
+            res["join"] = join_rows(path, fd, a, col)
     finally:
         os.close(fd)
     if a.strings:
@@ -445,7 +588,8 @@ def main(argv=None) -> int:
     if base_rows:
         res["arrow_scan_GBps"] = min(c["column_GBps"] for c in base_rows)
     res["verified"] = all(c["verified"] for c in res["columns"].values()) and \
-        all(r["verified"] for r in res.get("agg", {}).values())
+        all(r["verified"] for r in res.get("agg", {}).values()) and \
+        all(r["verified"] for r in res.get("join", {}).values())
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:

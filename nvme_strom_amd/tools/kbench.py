@@ -35,7 +35,8 @@ def main(argv=None):
     ap.add_argument("--gib", type=float, default=1.0)
     ap.add_argument("--only", default="crc,scatter,verify,heap,lz4,snappy,filter",
                     help="also: mvcc (snapshot check), par (LZ4 decoders by stream count), "
-                         "agg (aggregate kernels next to column_filter_i64)")
+                         "agg (aggregate kernels next to column_filter_i64), "
+                         "join (hash-join probe next to column_filter_i64)")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     only = set(a.only.split(","))
@@ -181,6 +182,8 @@ def main(argv=None):
         log("bitmap_to_indices", timed(lambda: bitmap_to_indices(bm, nv, cnt)), nv // 8 + cnt * 4)
     if "agg" in only:
         _agg_rows(n, dev, log, column_filter)
+    if "join" in only:
+        _join_rows(n, dev, log, column_filter)
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:
@@ -231,6 +234,44 @@ def _agg_rows(n, dev, log, column_filter):
     k = torch.full((nv,), 7, dtype=torch.int32, device=dev)
     row("column_agg_i64_sum_by256_skewed", A.Layout([A.Entry(A.SUM, "i8")], 256, 1), tv, tab(k),
         nv * 12)
+
+
+def _join_rows(n, dev, log, column_filter):
+    """The hash-join probe (coljoin.hip) alone on one HBM-resident record
+    batch of int64 foreign keys, half of them keys of the table: GB/s of the
+    fk bytes, next to column_filter_i64 of the same run on the same bitmap
+    geometry.  Table footprints of 64 KiB, 2 MiB, 64 MiB and 1 GiB (in an
+    XCD's L2, at its edge, in the Infinity Cache, in HBM) at 100 % and 1 %
+    (random) source selection; the ratio to the filter row says whether the
+    walk or the gather bounds the probe."""
+    from nvme_strom_amd.ops import coljoin as J
+    nv = n // 8
+    nwords = (nv + 63) // 64
+    v = torch.randint(-1000, 1000, (nv,), dtype=torch.int64, device=dev)
+    log("column_filter_i64", timed(lambda: column_filter(v, -100, 100), 20), nv * 8)
+    sels = {"100": torch.full((nwords,), -1, dtype=torch.int64, device=dev),
+            "1": column_filter(v, -10, 9)[0]}
+    del v
+    dst = torch.empty(nwords, dtype=torch.int64, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+    for tag, nbytes in (("64KiB", 64 << 10), ("2MiB", 2 << 20), ("64MiB", 64 << 20),
+                        ("1GiB", 1 << 30)):
+        nk = nbytes // 32                       # 16-byte slots, capacity = 2n
+        keys = torch.arange(nk, dtype=torch.int64, device=dev) * 2
+        table = J.build(keys, None)
+        del keys
+        fk = torch.randint(0, 2 * nk, (nv,), dtype=torch.int64, device=dev)
+        tab = torch.tensor([[fk.data_ptr(), 0, nv, 0, 0]], dtype=torch.int64, device=dev)
+        hdr = table.header()
+        assert int(hdr[J.H_NKEYS]) == nk and table.capacity * 16 == nbytes
+        for sel, bm in sels.items():
+            cnt.zero_()
+            log(f"column_join_i64_table{tag}_sel{sel}",
+                timed(lambda: J.probe(table, J.FK_CODE["i8"], tab, nwords, bm, dst, cnt), 20),
+                nv * 8)
+        print(f"column_join table {tag}: {nk} keys, largest displacement {int(hdr[J.H_MAXDISP])}",
+              file=sys.stderr, flush=True)
+        del fk, table
 
 
 def _mvcc_rows(n, dev, log):

@@ -483,11 +483,19 @@ int strom_zstd_release(void);
 /* the same decode on the CPU (the kernel's phases lane by lane) */
 int strom_zstd_host(int codec, const uint8_t *src, uint32_t src_len, uint8_t *dst, uint32_t cap);
 
-/* Columnar filter: bitmap[i/64] bit i%64 = valid(i) && lo <= v[i] <= hi. */
+/* Columnar filter: bitmap[i/64] bit i%64 = valid(i) && lo <= v[i] <= hi,
+ * the comparison exact against the double bounds (strom_filter_bounds). */
 #define STROM_COL_I32 1
 #define STROM_COL_I64 2
 #define STROM_COL_F32 3
 #define STROM_COL_F64 4
+/* The bounds the range filters compare with, in the column's own type
+ * (host; *lo_out / *hi_out receive one value of that type): integers
+ * ceil(lo) and floor(hi) clamped to the type, F32 the smallest float >= lo
+ * and the largest <= hi.  Returns 1, or 0 when no value can qualify (NaN on
+ * either side, lo > hi, the range past one end of the type): the bounds are
+ * then (1, 0) and the filters write zero words, count unchanged.  -22: type. */
+int strom_filter_bounds(int type, double lo, double hi, void *lo_out, void *hi_out);
 int strom_column_filter(int type, const void *d_values, const uint8_t *d_valid,
                         uint64_t n, double lo, double hi, uint64_t *d_bitmap,
                         uint64_t *d_count, void *stream);
@@ -523,8 +531,8 @@ int strom_column_filter_batched2(int type, const struct strom_filter_batch *d_ba
                                  uint32_t nbatches, uint64_t nwords, double lo, double hi,
                                  uint64_t *d_bitmap, uint64_t *d_count, int combine, void *stream);
 /* bitmap_to_rows + projection: d_proj (same batches, another column's
- * values/valid pointers) non-NULL gathers each selected row's value (width 4
- * or 8 bytes) into d_pout[pos] and, when d_pvalid, its validity (0/1). */
+ * values/valid pointers) non-NULL gathers each selected row's value (width 1,
+ * 2, 4, 8 or 16 bytes) into d_pout[pos] and, when d_pvalid, its validity (0/1). */
 int strom_bitmap_to_rows_proj(const uint64_t *d_bitmap, uint64_t nwords,
                               const struct strom_filter_batch *d_batches, uint32_t nbatches,
                               int64_t *d_out, uint64_t *d_total,
@@ -568,7 +576,9 @@ struct strom_col_qual {
 	uint64_t offs_bytes;
 };
 /* strom_filter_batch + aux (the character data of a string column, aux_len
- * bytes: offsets outside it never match and are never followed) */
+ * bytes: a row whose offsets are negative, decreasing or end past it is
+ * selected by no string operator, NEGATE or not, and is never followed; it
+ * still counts for STROM_QOP_VALID) */
 struct strom_qual_batch {
 	uint64_t values;
 	uint64_t valid;

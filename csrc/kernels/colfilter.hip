@@ -17,7 +17,9 @@
 // instruction per word, mostly inactive lanes) vs 6 + 12 + 40 us here.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -402,13 +404,48 @@ __global__ __launch_bounds__(256) void emit_str_kernel(const uint64_t *__restric
   }
 }
 
+// The double bounds of the range filter in the column's own type (the
+// kernels compare in T): integers ceil(lo) / floor(hi) clamped to the type,
+// float the smallest float >= lo and the largest <= hi.  False: no value of
+// T is inside (NaN on either side, lo > hi, both past one end of the type);
+// the bounds are then (1, 0), which the kernels select nothing with.
+template <typename T> struct IsFloatT { static constexpr bool value = false; };
+template <> struct IsFloatT<float> { static constexpr bool value = true; };
+template <> struct IsFloatT<double> { static constexpr bool value = true; };
+
+template <typename T>
+bool filter_bounds(double lo, double hi, T *plo, T *phi) {
+  *plo = (T)1;
+  *phi = (T)0;
+  if (lo != lo || hi != hi || lo > hi) return false;
+  T l, h;
+  if constexpr (IsFloatT<T>::value) {
+    l = (T)lo;                                   // round to nearest, then outwards-in
+    if ((double)l < lo) l = std::nextafter(l, std::numeric_limits<T>::infinity());
+    h = (T)hi;
+    if ((double)h > hi) h = std::nextafter(h, -std::numeric_limits<T>::infinity());
+  } else {
+    const double top = std::ldexp(1.0, (int)sizeof(T) * 8 - 1);   // max + 1, exact
+    const double cl = std::ceil(lo), fh = std::floor(hi);
+    if (cl >= top || fh < -top) return false;
+    l = cl < -top ? std::numeric_limits<T>::min() : (T)cl;
+    h = fh >= top ? std::numeric_limits<T>::max() : (T)fh;
+  }
+  if (l > h) return false;
+  *plo = l;
+  *phi = h;
+  return true;
+}
+
 template <typename T>
 int launch_filter_batched(const strom_filter_batch *bt, uint32_t nb, uint64_t nwords, double lo,
                           double hi, uint64_t *bm, uint64_t *cnt, int combine, hipStream_t st) {
   uint64_t g = (nwords + 4 * kU - 1) / (4 * kU);
   uint32_t grid = (uint32_t)(g > 8192 ? 8192 : (g ? g : 1));
-  hipLaunchKernelGGL(filter_batched_kernel<T>, dim3(grid), dim3(256), 0, st, bt, nb, nwords, (T)lo,
-                     (T)hi, bm, (unsigned long long *)cnt, combine);
+  T tlo, thi;
+  filter_bounds<T>(lo, hi, &tlo, &thi);
+  hipLaunchKernelGGL(filter_batched_kernel<T>, dim3(grid), dim3(256), 0, st, bt, nb, nwords, tlo,
+                     thi, bm, (unsigned long long *)cnt, combine);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
@@ -418,9 +455,11 @@ int launch_filter(const void *v, const uint8_t *valid, uint64_t n, double lo, do
   uint64_t words = (n + 63) / 64;
   uint64_t g = (words + 4 * kU - 1) / (4 * kU);
   uint32_t grid = (uint32_t)(g > 4096 ? 4096 : (g ? g : 1));
+  T tlo, thi;
+  filter_bounds<T>(lo, hi, &tlo, &thi);
   (void)hipMemsetAsync(cnt, 0, sizeof(uint64_t), st);
   hipLaunchKernelGGL(filter_kernel<T>, dim3(grid), dim3(256), 0, st, (const T *)v,
-                     (const uint64_t *)valid, n, (T)lo, (T)hi, bm, (unsigned long long *)cnt);
+                     (const uint64_t *)valid, n, tlo, thi, bm, (unsigned long long *)cnt);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
@@ -566,13 +605,14 @@ __global__ __launch_bounds__(256) void qual_kernel(strom_col_qual q,
   for (uint64_t w0 = ((uint64_t)blockIdx.x * 4 + wid) * U; w0 < nwords; w0 += step) {
     // pass 1: batch lookup + every lane's load of U words issued before the
     // first compare (kU rows per lane in flight, as filter_batched_kernel)
-    bool hit[U];
+    bool hit[U], bad[U];
     uint32_t bi[U];
     CT x[U];
 #pragma unroll
     for (uint32_t u = 0; u < U; ++u) {
       const uint64_t w = w0 + u;
       hit[u] = false;
+      bad[u] = false;
       bi[u] = 0;
       x[u] = 0;
       if (w >= nwords) continue;
@@ -604,9 +644,12 @@ __global__ __launch_bounds__(256) void qual_kernel(strom_col_qual q,
       } else {   // QK_STR: T is the offset type
         const int64_t s = (int64_t)((const T *)b.values)[i];
         const int64_t e = (int64_t)((const T *)b.values)[i + 1];
-        // a malformed offset pair (file data) never matches and is never
-        // followed outside the character buffer
-        if (s < 0 || e < s || (uint64_t)e > b.aux_len) continue;
+        // a malformed offset pair (file data) never matches, NEGATE or
+        // not, and is never followed outside the character buffer
+        if (s < 0 || e < s || (uint64_t)e > b.aux_len) {
+          bad[u] = true;
+          continue;
+        }
         const uint32_t len = (uint32_t)(e - s);
         const uint8_t *p = (const uint8_t *)b.aux + s;
         const uint32_t *offs = qs + cw;
@@ -635,6 +678,7 @@ __global__ __launch_bounds__(256) void qual_kernel(strom_col_qual q,
       const uint64_t vword = b.valid ? ((const uint64_t *)b.valid)[k] : ~0ull;
       uint64_t word;
       if (K == QK_VALID) word = __ballot(i < b.nrows && (((vword >> lane) & 1) != neg));
+      else if (K == QK_STR) word = __ballot(i < b.nrows && !bad[u] && (hit[u] != neg)) & vword;
       else word = __ballot(i < b.nrows && (hit[u] != neg)) & vword;
       if (or_src) word |= or_src[w];
       if (and_dst) word &= bitmap[w];
@@ -735,6 +779,17 @@ void *col_scratch(hipStream_t st, size_t bytes) {
 }
 
 }  // namespace
+
+extern "C" int strom_filter_bounds(int type, double lo, double hi, void *lo_out, void *hi_out) {
+  if (!lo_out || !hi_out) return -22;
+  switch (type) {
+    case STROM_COL_I32: return filter_bounds<int32_t>(lo, hi, (int32_t *)lo_out, (int32_t *)hi_out);
+    case STROM_COL_I64: return filter_bounds<int64_t>(lo, hi, (int64_t *)lo_out, (int64_t *)hi_out);
+    case STROM_COL_F32: return filter_bounds<float>(lo, hi, (float *)lo_out, (float *)hi_out);
+    case STROM_COL_F64: return filter_bounds<double>(lo, hi, (double *)lo_out, (double *)hi_out);
+    default: return -22;
+  }
+}
 
 extern "C" int strom_column_filter(int type, const void *d_values, const uint8_t *d_valid,
                                    uint64_t n, double lo, double hi, uint64_t *d_bitmap,

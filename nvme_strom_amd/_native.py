@@ -289,6 +289,7 @@ _SIGS = {
                                        C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "strom_decompress": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                    C.c_void_p, C.c_void_p]),
+    "strom_filter_bounds": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "strom_column_filter": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_double,
                                       C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "strom_bitmap_to_indices": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,

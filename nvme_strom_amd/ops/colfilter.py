@@ -14,7 +14,10 @@ _TYPES = {torch.int32: 1, torch.int64: 2, torch.float32: 3, torch.float64: 4}
 def column_filter(values: torch.Tensor, lo, hi, valid: Optional[torch.Tensor] = None,
                   stream=None) -> Tuple[torch.Tensor, int]:
     """Selection bitmap (int64 words, LSB-first like Arrow validity) of
-    ``lo <= v <= hi`` AND valid, plus the selected count."""
+    ``lo <= v <= hi`` AND valid, plus the selected count.  The comparison is
+    exact against the double bounds (the library converts them to the
+    column's type, strom_filter_bounds): ``+-inf`` leaves a side open, NaN
+    or ``lo > hi`` selects nothing."""
     require_cuda(values, "values")
     if values.dtype not in _TYPES:
         raise ValueError(f"unsupported dtype {values.dtype}")
@@ -91,7 +94,7 @@ def bitmap_to_rows(bitmap: torch.Tensor, nwords: int, batches: torch.Tensor, out
     ``cursor`` (int64[1], device) advances — successive groups of one scan
     fill ``out`` in order without a host round trip.  ``proj`` (a batch
     table of another column, same batches) gathers that column's value of
-    each selected row into ``proj_out[cursor]`` (1/2/4/8-byte elements),
+    each selected row into ``proj_out[cursor]`` (1/2/4/8/16-byte elements),
     and its validity (0/1) into ``proj_valid`` when given."""
     require_cuda(bitmap, "bitmap")
     if out.dtype != torch.int64:

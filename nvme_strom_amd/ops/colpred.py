@@ -51,6 +51,7 @@ QOP_RANGES, QOP_STR_IN, QOP_STR_PREFIX, QOP_LUT, QOP_VALID, QOP_STR_RANGES = 1, 
 FLAG_NEGATE, FLAG_NAN = 1, 2
 MAX_RANGES = 4096                 # the kernel stages constants in LDS (<= 64 KiB)
 MAX_CONST_BYTES = 48 << 10
+MAX_QUAL_BYTES = 64 << 10         # strom_column_qual: constants + string offsets
 MAX_LUT_BITS = 512 << 10
 
 OPS = {"==", "!=", "<", "<=", ">", ">=", "between", "in", "not in", "ranges", "prefix",
@@ -387,8 +388,10 @@ def _string_ranges(op: str, v, col: Column, code: int, flags: int) -> Compiled:
             b = b or b""
             offs += [len(blob), len(b), m]
             blob += b + b"\0" * (-len(b) % 4)
-    if len(blob) > MAX_CONST_BYTES or len(rs) > MAX_RANGES:
-        raise ValueError(f"column {col.name}: {len(rs)} string ranges, {len(blob)} bytes")
+    if len(blob) > MAX_CONST_BYTES or len(rs) > MAX_RANGES or \
+            len(blob) + 24 * len(rs) > MAX_QUAL_BYTES:
+        raise ValueError(f"column {col.name}: {len(rs)} string ranges, {len(blob)} bytes "
+                         f"(device limit {MAX_QUAL_BYTES} bytes with 24 per range)")
     return Compiled(code, QOP_STR_RANGES, flags, len(rs), bytes(blob) or b"\0\0\0\0",
                     np.asarray(offs, np.uint32).tobytes(), strings=rs)
 
@@ -416,16 +419,19 @@ def _compile_value(p: Pred, col: Column, dt: str, code: int) -> Compiled:
         for b in vals:
             offs += [len(blob), len(b)]
             blob += b + b"\0" * (-len(b) % 4)
-        if len(blob) > MAX_CONST_BYTES or len(vals) > MAX_RANGES:
+        if len(blob) > MAX_CONST_BYTES or len(vals) > MAX_RANGES or \
+                len(blob) + 8 * len(vals) > MAX_QUAL_BYTES:
             raise ValueError(f"column {col.name}: {len(vals)} string constants, "
-                             f"{len(blob)} bytes (device limit {MAX_CONST_BYTES} bytes)")
+                             f"{len(blob)} bytes (device limit {MAX_CONST_BYTES} bytes, "
+                             f"{MAX_QUAL_BYTES} with 8 per constant)")
         return Compiled(code, qop, flags, len(vals), bytes(blob) or b"\0\0\0\0",
                         np.asarray(offs or [0, 0], np.uint32).tobytes(), strings=vals)
     if base == "prefix":
         raise ValueError(f"column {col.name} ({col.kind}): prefix needs utf8/binary")
     rs, extra = _num_ranges(base, p.value, col, dt)
-    if len(rs) > MAX_RANGES:
-        raise ValueError(f"column {col.name}: {len(rs)} disjoint ranges (limit {MAX_RANGES})")
+    limit = min(MAX_RANGES, MAX_QUAL_BYTES // (32 if dt == "d16" else 16))
+    if len(rs) > limit:
+        raise ValueError(f"column {col.name}: {len(rs)} disjoint ranges (limit {limit})")
     if dt == "d16":
         # 128-bit bounds, (lo, hi) pairs of little-endian two's complement
         blob = b"".join(int(x).to_bytes(16, "little", signed=True) for r in rs for x in r)
@@ -474,6 +480,20 @@ def compile_pred(p: Pred, col: Column, dictionary=None) -> Compiled:
 
 
 # ------------------------------------------------------------ numpy twin
+def _str_rows(values, n: int, ok: np.ndarray):
+    """(start, length, characters, ok) of n rows of a utf8/binary column.
+    A row whose offset pair is negative, decreasing or ends past the
+    characters (file data) is selected by no string operator, negated or
+    not (as the kernel): it leaves ``ok`` and reads as an empty string."""
+    offs, data = values
+    offs = np.asarray(offs[:n + 1], np.int64)
+    if not isinstance(data, np.ndarray):
+        data = np.frombuffer(bytes(data), np.uint8)
+    a, e = offs[:-1], offs[1:]
+    bad = (a < 0) | (e < a) | (e > len(data))
+    return np.where(bad, 0, a), np.where(bad, 0, e - a), data, ok & ~bad
+
+
 def evaluate(c: Compiled, values, valid: Optional[np.ndarray], n: int) -> np.ndarray:
     """The kernel's bits for n rows on the host: values as
     arrow_ipc.decode_values returns them (indices for a LUT)."""
@@ -507,9 +527,7 @@ def evaluate(c: Compiled, values, valid: Optional[np.ndarray], n: int) -> np.nda
         if c.flags & FLAG_NAN:
             hit |= np.isnan(x)
     elif c.op in (QOP_STR_IN, QOP_STR_PREFIX):
-        offs, data = values
-        offs = np.asarray(offs[:n + 1], np.int64)
-        ln = offs[1:] - offs[:-1]
+        st, ln, data, ok = _str_rows(values, n, ok)
         hit = np.zeros(n, bool)
         for s in c.strings:
             L = len(s)
@@ -518,13 +536,12 @@ def evaluate(c: Compiled, values, valid: Optional[np.ndarray], n: int) -> np.nda
                 hit[cand] = True
                 continue
             ref = np.frombuffer(s, np.uint8)
-            m = data[offs[cand][:, None] + np.arange(L)[None, :]] == ref[None, :]
+            m = data[st[cand][:, None] + np.arange(L)[None, :]] == ref[None, :]
             hit[cand[m.all(axis=1)]] = True
     elif c.op == QOP_STR_RANGES:
-        offs, data = values
-        offs = np.asarray(offs[:n + 1], np.int64)
-        raw = data.tobytes() if hasattr(data, "tobytes") else bytes(data)
-        col = [raw[offs[i]:offs[i + 1]] for i in range(n)]
+        st, ln, data, ok = _str_rows(values, n, ok)
+        raw = data.tobytes()
+        col = [raw[st[i]:st[i] + ln[i]] for i in range(n)]
         hit = np.zeros(n, bool)
         for lo, lm, hi, hm in c.strings:
             ok_lo = [True] * n if not lm else [x >= lo if lm == 1 else x > lo for x in col]

@@ -1118,6 +1118,11 @@ HD void st_header(Smem &s, const Ctx &c, int codec) {
         return;
       }
       b = c.in[p++];
+      if (sh == 28 && (b & 0x70)) {      // a length of 2^32 or more: no capacity holds it
+        s.err = kErrOverflow;
+        s.mode = kModeDone;
+        return;
+      }
       ul |= (b & 0x7fu) << sh;
       sh += 7;
     } while (b & 0x80);
@@ -1143,6 +1148,13 @@ HD void st_header(Smem &s, const Ctx &c, int codec) {
     s.bend = c.len;
     s.braw = 1;
     s.raw_block = 2;                              // one stored block, then done
+    return;
+  }
+  // the prefix is the buffer's decoded length: one above the capacity is an
+  // overflow whatever the frame behind it holds (as in decompress.hip)
+  if (hi != 0 || lo > c.cap) {
+    s.err = kErrOverflow;
+    s.mode = kModeDone;
     return;
   }
   uint32_t p = 8;

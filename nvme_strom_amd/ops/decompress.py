@@ -255,7 +255,10 @@ def decompress_async(codec: int, src: torch.Tensor, dst: torch.Tensor, d_desc: t
 def decompress(codec: int, src: torch.Tensor, dst: torch.Tensor, descs: np.ndarray,
                stream=None) -> np.ndarray:
     """Decode every stream described by ``descs``; returns per-stream status
-    (decoded byte count, or <0: -1 malformed, -2 overflow)."""
+    (decoded byte count, or <0: -1 malformed, -2 overflow: the stream, its
+    snappy preamble or its Arrow length prefix asks for more than the
+    capacity; the block-parallel decoder reports a match that starts before
+    the output as -3 rather than -1)."""
     require_cuda(src, "src")
     require_cuda(dst, "dst")
     descs = np.ascontiguousarray(descs, dtype=DESC_DTYPE)

@@ -711,6 +711,62 @@ int strom_column_join(int type, int how, const uint64_t *d_table, uint64_t capac
                       const uint64_t *d_src, uint64_t *d_dst,
                       const struct strom_filter_batch *d_kout, uint64_t *d_count, void *stream);
 
+/* Hash GROUP BY on an integer key column (csrc/kernels/colgroup.hip; Arrow
+ * scans: by=HashBy(col) of ArrowScan.aggregate) for key domains that do not
+ * fit strom_column_agg's LDS.
+ *
+ * The table is STROM_GROUP_HDR_WORDS + capacity 64-bit words on the device:
+ * the header, then one key word per slot, open addressing with linear probing
+ * from strom_join_hash(key) & (capacity - 1).  capacity is a power of two
+ * >= 2 * groups (strom_group_capacity), at most STROM_GROUP_MAX_CAPACITY.  A
+ * key is the 64-bit pattern of the column's value (signed types sign-extended,
+ * unsigned ones zero-extended).  A free slot holds STROM_JOIN_EMPTY; the key
+ * with that pattern is legal and has the reserved code capacity + 1, the null
+ * keys have code capacity.  Header: NKEYS the distinct non-null keys that got
+ * a code, OVERFLOW the selected rows that found no slot, HAS_EMPTY whether the
+ * key STROM_JOIN_EMPTY was met.
+ *
+ * Accumulators: per entry popcount(ops) arrays of capacity + 2 words in the
+ * order and encoding of strom_column_agg, indexed by code.  strom_group_init
+ * clears the table and sets the arrays at e[i].acc to their identities
+ * (e[i].type, vals and slabs are not read); nothing else ever writes a word
+ * of either without an atomic.
+ *
+ * strom_group_codes walks a selection bitmap like strom_column_join: each
+ * selected row that exists finds or inserts its key and gets its int32 code
+ * written at its row of d_codes (a table of the same batches whose values
+ * point to int32 buffers of nrows elements).  d_dst[w] = d_src[w] over the rows
+ * that exist, minus the rows that found no slot (their code is written as 0);
+ * d_dst may be d_src.  type as for strom_column_join, U64 over its whole range.
+ * Launches on different streams may share a table.
+ *
+ * strom_group_agg adds one entry's column over the bitmap into the arrays at
+ * d_acc with device-scope atomics (no slabs, no reduce: float sums depend on
+ * arrival order); a code outside [0, capacity + 2) is not followed.  combine
+ * != 0: in a word of mixed codes the rows that share the first selected row's
+ * code (when there are two or more) stay in the wave's registers, as a word of
+ * one code does, and are added when that code changes. */
+#define STROM_GROUP_HDR_WORDS 8
+#define STROM_GROUP_MAX_CAPACITY (1ull << 25)
+#define STROM_GROUP_H_CAPACITY 0
+#define STROM_GROUP_H_NKEYS 1
+#define STROM_GROUP_H_OVERFLOW 2
+#define STROM_GROUP_H_HAS_EMPTY 3
+uint64_t strom_group_capacity(uint64_t groups);
+int strom_group_init(uint64_t *d_table, uint64_t capacity, const struct strom_agg_entry *e,
+                     uint32_t n, void *stream);
+int strom_group_codes(int type, uint64_t *d_table, uint64_t capacity,
+                      const struct strom_filter_batch *d_keys, uint32_t nbatches, uint64_t nwords,
+                      const uint64_t *d_src, uint64_t *d_dst,
+                      const struct strom_filter_batch *d_codes, void *stream);
+int strom_group_agg(int type, uint32_t ops, const uint64_t *d_bitmap, uint64_t nwords,
+                    const struct strom_filter_batch *d_vals,
+                    const struct strom_filter_batch *d_codes, uint32_t nbatches, uint64_t *d_acc,
+                    uint64_t capacity, int combine, void *stream);
+int strom_group_agg_many(const struct strom_agg_entry *e, uint32_t n, const uint64_t *d_bitmap,
+                         uint64_t nwords, const struct strom_filter_batch *d_codes,
+                         uint32_t nbatches, uint64_t capacity, int combine, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -330,6 +330,15 @@ _SIGS = {
     "strom_column_join": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
                                     C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "strom_group_capacity": (C.c_uint64, [C.c_uint64]),
+    "strom_group_init": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "strom_group_codes": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                    C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "strom_group_agg": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                  C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int,
+                                  C.c_void_p]),
+    "strom_group_agg_many": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                       C.c_uint32, C.c_uint64, C.c_int, C.c_void_p]),
     "strom_io_info": (C.c_int, [C.c_void_p]),
     "strom_io_prof": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "strom_arrow_headers": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,

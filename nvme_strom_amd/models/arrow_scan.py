@@ -32,7 +32,7 @@ from __future__ import annotations
 import os
 import struct
 import time
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -40,6 +40,7 @@ import torch
 
 from .. import api
 from ..ops import colagg as A
+from ..ops import colgroup as G
 from ..ops import coljoin as J
 from ..ops import decompress as D
 from ..ops.colfilter import BATCH_FIELDS, bitmap_to_rows, bitmap_to_rows_str
@@ -194,6 +195,24 @@ class Join:
         self.col, self.table, self.how = str(col), table, how
 
 
+class HashBy:
+    """``by=HashBy("customer_id", groups=1 << 20)``: GROUP BY an ordinary
+    integer column (int8-int64, uint8-uint64 over its whole range, or a date /
+    time / timestamp / duration column by its ticks) through a hash table in
+    HBM (csrc/kernels/colgroup.hip) instead of the key-indexed accumulators
+    in LDS that ``by="name"`` uses.  ``groups``: the largest number of
+    distinct non-null keys the scan may meet, 1 <= groups <= 2^24; the table
+    gets the next power of two >= 2 * groups slots and is not grown: a scan
+    that meets more keys raises RuntimeError at its one sync."""
+
+    def __init__(self, col: str, groups: int = 1 << 16):
+        self.col = str(col)
+        self.groups = G.check_groups(groups)
+
+    def __repr__(self) -> str:
+        return f"HashBy({self.col!r}, groups={self.groups})"
+
+
 def _check_join(meta: ArrowFile, join, attr) -> Optional[Join]:
     """Validate ``join=`` and the JoinAttr of ``by=`` / ``project=`` (or
     None) against the schema."""
@@ -247,6 +266,14 @@ class _JoinRun:
     how: str
     dev: J.DeviceTable
     attr: Optional[str] = None    # attribute whose codes the probe writes
+
+
+@dataclass
+class _HashRun:
+    """A scan's hash GROUP BY as _compute sees it."""
+    col: int                      # plan column of the key
+    code: int                     # its STROM_COL_* storage type
+    dev: G.DeviceGroups
 
 
 @dataclass
@@ -951,12 +978,45 @@ class ArrowScan:
                 J.probe(jn.dev, jn.code, d_j[0], g.words, bitmap, s.bitmap, s.count,
                         how=J.HOW[jn.how], key_out=d_kout, stream=cs)
                 bitmap = s.bitmap
+            hs = state.get("hash")
+            if hs is not None:
+                # by=HashBy: find-or-insert of the key column over the bitmap
+                # the qualifiers and the probe left; each row's code goes into
+                # the slot's key buffer, the accumulate launches' key column
+                if s.keybuf is None or s.keybuf.numel() < s.bitmap.numel() * 64:
+                    s.keybuf = torch.empty(s.bitmap.numel() * 64, dtype=torch.int32,
+                                           device=self.device)
+                key5 = (tabs_np[hs.col] if hs.col in tabs_np else
+                        self._pointers(g, hs.col, base, dec_base))[:, :BATCH_FIELDS]
+                c5 = key5.copy()
+                c5[:, 0] = s.keybuf.data_ptr() + g.table[:, 3] * 256
+                c5[:, 1] = 0
+                d_h = self._upload(s, np.stack([key5, c5]))
+                s.keep.append(d_h)
+                G.group_codes(hs.dev, hs.code, d_h[0], g.words, bitmap, s.bitmap, d_h[1],
+                              stream=cs)
+                bitmap = s.bitmap
+                kout_ptr = d_h[1].data_ptr()
             state["marks"].append((k, "quals_queued", time.perf_counter()))
             # emit tables: the strom_filter_batch prefix of the qual tables
             any_col = spec[0][0][0] if spec else (jn.col if jn is not None else 0)
             d_rows = table(any_col)[:, :BATCH_FIELDS].contiguous()
             agg = state.get("agg")
-            if agg is not None:
+            if agg is not None and hs is not None:
+                # the accumulate launches add into the table's arrays in HBM:
+                # no slabs, nothing left for the emit stream to fold
+                n = len(g.table)
+                cols = sorted({any_col if c is None else c for c in agg.entry_cols})
+                t5 = np.stack([(tabs_np[c] if c in tabs_np else
+                                self._pointers(g, c, base, dec_base))[:, :BATCH_FIELDS]
+                               for c in cols])
+                d_t5 = self._upload(s, t5)
+                s.keep.append(d_t5)
+                for e, c in enumerate(agg.entry_cols):
+                    hs.dev.args[e].vals = d_t5.data_ptr() + \
+                        cols.index(any_col if c is None else c) * n * BATCH_FIELDS * 8
+                G.group_agg_many(hs.dev, bitmap, g.words, kout_ptr, n, stream=cs)
+            elif agg is not None:
                 # one aggregate launch per aggregated column on the slot's
                 # stream, each leaving its workgroups' slabs.  The host's time
                 # here delays the next group's read: the columns' batch
@@ -1002,7 +1062,8 @@ class ArrowScan:
         with torch.cuda.stream(es):
             if agg is not None:
                 # the slabs into the scan's accumulator block, in group order
-                A.agg_reduce_many(agg.layout, args, g.words, stream=es)
+                if hs is None:
+                    A.agg_reduce_many(agg.layout, args, g.words, stream=es)
             elif pstr:
                 bitmap_to_rows_str(s.bitmap, g.words, d_rows, state["out"], state["cursor"],
                                    d_proj, state["owidth"], state["poff"], state["pchars"],
@@ -1200,18 +1261,26 @@ class ArrowScan:
         bits, float sums are float64; NaN propagates into a sum and is
         ignored by min / max; nulls are skipped.  ``by``: a
         dictionary-encoded, bool or 8-bit integer column (null keys form a
-        group of their own, key None).  ``join=`` as in scan_where: only the
+        group of their own, key None), or ``HashBy(col, groups)`` for an
+        ordinary integer or temporal column of up to ``groups`` distinct
+        values: a hash table in HBM (csrc/kernels/colgroup.hip) gives each
+        row a code and the accumulators are updated with global atomics —
+        rows come back ascending by key, the null group last, and float sums
+        are not bitwise reproducible from run to run (the keyed LDS path's are
+        not either).  More than ``groups`` distinct keys raise RuntimeError at
+        the scan's sync; there is no retry.  ``join=`` as in scan_where: only the
         joined rows are aggregated, and ``by=dim[attr]`` groups them by an
         attribute of the JoinTable — the probe writes each row's attribute
         code into the slot's key buffer and the aggregate kernels take it as
         their key column.  See AggOut."""
         t0 = time.perf_counter()
         battr = by if isinstance(by, JoinAttr) else None
+        hb = by if isinstance(by, HashBy) else None
         join = _check_join(self.meta, join, battr)
-        if battr is not None:
+        if battr is not None or hb is not None:
             by = None
         cl = clauses(quals) if quals else []
-        agg = _agg_spec(self.meta, aggs, by, self.dictionary, battr)
+        agg = _agg_spec(self.meta, aggs, by, self.dictionary, battr, hb)
         names: List[str] = []
         for n in [p.col for c in cl for p in c] + ([join.col] if join else []) + agg.names:
             if n not in names:
@@ -1234,6 +1303,9 @@ class ArrowScan:
         cols, nrows, groups = self._plans[key]
         spec = [[(names.index(p.col), self._compile(p)) for p in c] for c in cl]
         t_plan = time.perf_counter()
+        if hb is not None and (not groups or nrows == 0):
+            return _hash_out(agg, G.empty_groups(agg.layout.entries, agg.hash_unsigned), nrows,
+                             {"total_s": time.perf_counter() - t0})
         if not groups or nrows == 0:
             return _agg_out(agg, A.new_block(agg.layout), nrows,
                             {"total_s": time.perf_counter() - t0})
@@ -1247,10 +1319,19 @@ class ArrowScan:
         # the block is initialised on the emit stream, where the reduces follow
         with torch.cuda.stream(self.emit_stream):
             block = A.alloc_block(agg.layout, self.device, stream=self.emit_stream)
+            dev = None
+            if hb is not None:
+                # the table and its accumulators, initialised before any
+                # launch can see a slot (block_ready below)
+                dev = G.DeviceGroups(agg.layout.entries, hb.groups, self.device,
+                                     agg.hash_unsigned, stream=self.emit_stream)
         state = dict(agg=agg, block=block, count=z(), err=z(), wait_s=0.0, bytes_read=0,
                      column_bytes=0, marks=[])
         if join is not None:
             state["join"] = self._join_run(join, names, battr)
+        if hb is not None:
+            kc = self.meta.schema[self.meta.column_index(hb.col)]
+            state["hash"] = _HashRun(names.index(hb.col), G.KEY_CODE[kc.storage], dev)
         # the aggregate launches (slot streams) count malformed keys in the
         # block: they must see it initialised
         ready = torch.cuda.Event()
@@ -1265,6 +1346,12 @@ class ArrowScan:
             self._compute(k, spec, None, state)
             if k + ahead < len(groups):
                 self._submit(k + ahead, groups[k + ahead])
+        if dev is not None:
+            # behind the last group on the emit stream: the occupied slots
+            # and the two reserved codes, compacted; only they and the header
+            # are read back
+            with torch.cuda.stream(self.emit_stream):
+                hdr, found = G.compact(dev)
         torch.cuda.synchronize(self.device)
         err = int(state["err"].item())
         host = A.block_to_host(block)
@@ -1275,6 +1362,17 @@ class ArrowScan:
         if err:
             raise RuntimeError(f"{'ZSTD' if self._codec == D.ARROW_ZSTD else 'LZ4'} decode "
                                f"failed for {err} buffer(s) of columns {names}")
+        secs = {"plan_s": t_plan - t0, "alloc_s": t_alloc - t_plan,
+                "wait_s": state["wait_s"], "total_s": t_end - t0}
+        if dev is not None:
+            nk, over = int(hdr[G.H_NKEYS]), int(hdr[G.H_OVERFLOW])
+            if nk > hb.groups or over:
+                seen = f"{nk} distinct keys seen" if not over else \
+                    f"the table is full ({nk} keys in it, {over} selected row(s) found no slot)"
+                raise RuntimeError(f"GROUP BY HashBy({hb.col!r}): more than groups={hb.groups} "
+                                   f"distinct keys: {seen}; scan again with a larger groups=")
+            return _hash_out(agg, found, nrows, secs, bytes_read=state["bytes_read"],
+                             column_bytes=state["column_bytes"], groups=len(groups))
         return _agg_out(agg, host, nrows,
                         {"plan_s": t_plan - t0, "alloc_s": t_alloc - t_plan,
                          "wait_s": state["wait_s"], "total_s": t_end - t0},
@@ -1459,10 +1557,12 @@ class _AggSpec:
     key_col: Optional[int] = None
     slab_words: Dict[int, List[int]] = field(default_factory=dict)   # by group words
     join_attr: bool = False                 # ``by`` names a JoinTable attribute
+    hashed: bool = False                    # by=HashBy(by): layout / keyvals per result
+    hash_unsigned: bool = False             # its keys are uint64
 
 
 def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary,
-              jattr: Optional[JoinAttr] = None) -> _AggSpec:
+              jattr: Optional[JoinAttr] = None, hb: Optional[HashBy] = None) -> _AggSpec:
     """Validate ``aggs`` / ``by`` against the schema and lay the accumulator
     block out: entry 0 counts the selected rows per slot, then one entry per
     aggregated column with COUNT and whatever of SUM / MIN / MAX is asked."""
@@ -1517,8 +1617,22 @@ def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary,
         else:
             raise NotImplementedError(
                 f"GROUP BY {by}: {k.kind} keys (dictionary-encoded, bool and 8-bit integer "
-                "columns are grouped on the GPU)")
+                "columns are grouped on the GPU by name; by=HashBy(column) groups an integer "
+                "or temporal column of any width)")
         nslots = len(keyvals) + 1
+    if hb is not None:
+        if jattr is not None:
+            raise ValueError("by=: a JoinTable attribute or HashBy, not both")
+        if hb.col not in schema:
+            raise ValueError(f"no column {hb.col!r}")
+        k = schema[hb.col]
+        if k.dictionary is not None or k.kind not in ("int",) + _TEMPORAL or \
+                k.storage not in G.KEY_CODE:
+            kind = "dictionary-encoded" if k.dictionary is not None else k.kind
+            raise NotImplementedError(
+                f"GROUP BY HashBy({hb.col}): {kind} keys (integer and date / time / timestamp / "
+                "duration columns are hashed; dictionary-encoded, bool and 8-bit columns are "
+                "grouped by name)")
     if jattr is not None:
         # the key column is the probe's int32 code buffer; every selected row
         # matched, so the null slot stays empty (the kernels want two slots)
@@ -1532,6 +1646,12 @@ def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary,
     names = [n for n in entry_names[1:]]
     if by is not None and by not in names:
         names.append(by)
+    if hb is not None:
+        if hb.col not in names:
+            names.append(hb.col)
+        return _AggSpec(aggs, hb.col, A.Layout(entries), entry_names, names,
+                        {n: schema[n] for n in names}, None, hashed=True,
+                        hash_unsigned=schema[hb.col].storage[0] == "u")
     return _AggSpec(aggs, by if jattr is None else jattr.name,
                     A.Layout(entries, nslots, key_code), entry_names, names,
                     {n: schema[n] for n in names}, keyvals, join_attr=jattr is not None)
@@ -1543,7 +1663,9 @@ class AggOut:
 
     One row per group that selected anything, in slot order (dictionary
     index / False, True / byte value), the null-key group last; without
-    ``by`` exactly one row.  ``values[i]`` / ``valid[i]`` belong to
+    ``by`` exactly one row; with ``by=HashBy(col)`` ``keys`` are Python ints
+    (ticks for a temporal column) ascending by value, signed or unsigned as
+    the column is, the null group last.  ``values[i]`` / ``valid[i]`` belong to
     ``aggs[i]``: sums are int64 / uint64 / float64, min and max have the
     column's storage dtype (ticks for temporal columns: ``columns[i]`` holds
     the type), mean is float64(sum) / count; a group whose column counted
@@ -1563,6 +1685,7 @@ class AggOut:
     groups: int = 0
     _spec: Optional[_AggSpec] = None
     _block: Optional[np.ndarray] = None
+    _found: Optional[G.Groups] = None       # by=HashBy: key -> accumulators
 
     def get(self, fn: str, col: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray]:
         """(values, valid) of one requested aggregate."""
@@ -1574,10 +1697,20 @@ class AggOut:
         ``by`` of the same file (other record batches, another rank):
         counts and sums add, min and max combine."""
         a, b = self._spec, other._spec
+        secs = {"total_s": self.seconds.get("total_s", 0.0) + other.seconds.get("total_s", 0.0)}
+        if a.hashed or b.hashed:
+            # by=HashBy: the union of the keys, whatever groups= each scan had
+            if not (a.hashed and b.hashed):
+                raise ValueError("merge: a HashBy result merges with HashBy results only")
+            if a.aggs != b.aggs or a.by != b.by or a.hash_unsigned != b.hash_unsigned:
+                raise ValueError("merge: different aggregates or HashBy column")
+            return _hash_out(a, G.merge(self._found, other._found), self.rows + other.rows, secs,
+                             bytes_read=self.bytes_read + other.bytes_read,
+                             column_bytes=self.column_bytes + other.column_bytes,
+                             groups=self.groups + other.groups)
         if a.aggs != b.aggs or a.by != b.by or a.layout.nslots != b.layout.nslots or \
                 a.keyvals != b.keyvals or a.join_attr != b.join_attr:
             raise ValueError("merge: different aggregates, key, dictionary or join attribute")
-        secs = {"total_s": self.seconds.get("total_s", 0.0) + other.seconds.get("total_s", 0.0)}
         return _agg_out(a, A.merge_blocks(a.layout, self._block, other._block),
                         self.rows + other.rows, secs,
                         bytes_read=self.bytes_read + other.bytes_read,
@@ -1598,7 +1731,12 @@ def _agg_out(spec: _AggSpec, block: np.ndarray, rows: int, seconds: Dict[str, fl
         keys = None
     else:
         show = np.flatnonzero(count_all > 0)
-        keys = [spec.keyvals[s] if s < lay.nslots - 1 else None for s in show.tolist()]
+        if spec.hashed:
+            # possibly millions of groups: no Python per key
+            nn = show[show < lay.nslots - 1]
+            keys = spec.keyvals[nn].tolist() + [None] * (len(show) - len(nn))
+        else:
+            keys = [spec.keyvals[s] if s < lay.nslots - 1 else None for s in show.tolist()]
     ent = {n: A.entry_arrays(lay, block, e) for e, n in enumerate(spec.entry_names) if e}
     values, valid, columns = [], [], []
     for fn, col in spec.aggs:
@@ -1625,6 +1763,16 @@ def _agg_out(spec: _AggSpec, block: np.ndarray, rows: int, seconds: Dict[str, fl
                   valid, columns, seconds, bytes_read, column_bytes, groups, spec, block)
 
 
+def _hash_out(spec: _AggSpec, found: G.Groups, rows: int, seconds: Dict[str, float],
+              **kw) -> AggOut:
+    """The AggOut of a by=HashBy result: ``found``'s keys (ascending by
+    value) are the slots of a block of its own layout."""
+    per = replace(spec, layout=found.layout, keyvals=found.keys)
+    out = _agg_out(per, found.block, rows, seconds, **kw)
+    out._found = found
+    return out
+
+
 def host_aggregate(path: str, quals, aggs, by=None,
                    batches: Optional[Tuple[int, int]] = None, meta: Optional[ArrowFile] = None,
                    dicts: Optional[dict] = None, join: Optional[Join] = None) -> AggOut:
@@ -1643,10 +1791,12 @@ def host_aggregate(path: str, quals, aggs, by=None,
             dicts[name] = dictionary_values(meta, schema[name][1], path)
         return dicts[name]
     battr = by if isinstance(by, JoinAttr) else None
+    hb = by if isinstance(by, HashBy) else None
     join = _check_join(meta, join, battr)
-    if battr is not None:
+    if battr is not None or hb is not None:
         by = None
-    spec = _agg_spec(meta, aggs, by, dictionary, battr)
+    spec = _agg_spec(meta, aggs, by, dictionary, battr, hb)
+    found = G.empty_groups(spec.layout.entries, spec.hash_unsigned) if hb is not None else None
     comp = []
     for c in cl:
         row = []
@@ -1676,7 +1826,7 @@ def host_aggregate(path: str, quals, aggs, by=None,
                 vraw = read_buffer(src, ch.validity, b.codec) if ch.null_count else b""
                 ok = validity_bits(vraw, ch.length)
                 if not any(n == q for c in comp for q, _ in c) and n != by and \
-                        not (join and n == join.col) and \
+                        not (join and n == join.col) and not (hb and n == hb.col) and \
                         lay.entries[spec.entry_names.index(n)].dtype is None:
                     data[n] = (None, ok)          # counted only: its validity is enough
                     continue
@@ -1707,9 +1857,22 @@ def host_aggregate(path: str, quals, aggs, by=None,
                 if kv.dtype == np.int8 and schema[by][1].dictionary is None:
                     kv = kv.view(np.uint8)        # 8-bit key: the slot is the byte
                 key = (kv, kok)
+            if hb is not None:
+                # the hash path's twin: this batch's groups, united by key
+                kv, kok = data[hb.col]
+                found = G.merge(found, G.host_group_agg(
+                    lay.entries, m, kv, kok,
+                    [(None, None) if name is None else data[name] for name in spec.entry_names]))
+                continue
             for e, name in enumerate(spec.entry_names):
                 v, ok = (None, None) if name is None else data[name]
                 A.host_agg(lay, block, e, m, v, ok, key, count_bad=e == 0)
     finally:
         src.close()
+    if hb is not None:
+        if len(found.keys) > hb.groups:
+            raise RuntimeError(f"GROUP BY HashBy({hb.col!r}): more than groups={hb.groups} "
+                               f"distinct keys: {len(found.keys)} distinct keys seen; scan again "
+                               "with a larger groups=")
+        return _hash_out(spec, found, nrows, {"total_s": time.perf_counter() - t0})
     return _agg_out(spec, block, nrows, {"total_s": time.perf_counter() - t0})

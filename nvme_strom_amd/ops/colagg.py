@@ -27,7 +27,8 @@ COUNT, SUM, MIN, MAX, ALL = 1, 2, 4, 8, 16
 COL_NONE = 0
 COL_BOOL = 11
 # a launch keeps popcount(ops) * nslots 8-byte accumulators in LDS
-# (STROM_AGG_LDS_BYTES); there is no global-memory path for larger key domains
+# (STROM_AGG_LDS_BYTES); larger integer key domains go through the hash table
+# and HBM accumulators of ops/colgroup.py
 LDS_BYTES = 64 << 10
 _SIGN = np.uint64(1 << 63)
 _ONES = np.uint64(0xFFFFFFFFFFFFFFFF)

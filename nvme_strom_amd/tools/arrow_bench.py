@@ -405,6 +405,72 @@ def join_rows(path: str, fd: int, a, col) -> dict:
     return rows
 
 
+def hashagg_row(path: str, fd: int, a, col) -> dict:
+    """``aggregate([x range], [count(*), sum(id), max(x)], by=HashBy("val",
+    groups=1 << 20))`` — ``val`` has a million distinct values, an id-like
+    key — alternated with the same aggregates without a key (the same columns
+    read and decoded; the hash step and the atomics are the difference).  The
+    file is evicted before every run; verified against numpy."""
+    import torch
+
+    import nvme_strom_amd as S
+    from nvme_strom_amd.models.arrow_scan import ArrowScan, HashBy
+    quals = [("x", 0.25, 0.75)]
+    aggs = [("count", None), ("sum", "id"), ("max", "x")]
+    sc = ArrowScan(path, "cuda", slot_bytes=a.slot_mib << 20, nslots=a.nslots or None,
+                   chunk_sz=(a.chunk_kib << 10) or None)
+
+    def timed(fn):
+        S.evict_file(fd)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t, out
+    hash_s, flat_s = [], []
+    try:
+        by = HashBy("val", groups=1 << 20)
+        timed(lambda: sc.aggregate(quals, aggs, by=by))           # cold: plans, slots, code
+        timed(lambda: sc.aggregate(quals, aggs + [("count", "val")]))
+        for k in range(max(1, a.agg_pairs)):
+            for what in (("hash", "flat") if k % 2 == 0 else ("flat", "hash")):
+                if what == "hash":
+                    dt, out = timed(lambda: sc.aggregate(quals, aggs, by=by))
+                    hash_s.append(dt)
+                else:
+                    dt, flat = timed(lambda: sc.aggregate(quals, aggs + [("count", "val")]))
+                    flat_s.append(dt)
+            _log(f"hashagg pair {k}: HashBy {hash_s[-1] * 1e3:.1f} ms, no key "
+                 f"{flat_s[-1] * 1e3:.1f} ms")
+    finally:
+        sc.close()
+    xv, xok = col("x")
+    m = (xv >= 0.25) & (xv <= 0.75)
+    if xok is not None:
+        m &= xok
+    val = col("val")[0][m]
+    keys, inv = np.unique(val, return_inverse=True)
+    want_sum = np.zeros(len(keys), np.int64)
+    np.add.at(want_sum, inv, col("id")[0][m])
+    want_max = np.full(len(keys), -np.inf)
+    np.maximum.at(want_max, inv, xv[m])
+    ok = bool(out.keys == keys.tolist() and
+              np.array_equal(out.count_all, np.bincount(inv, minlength=len(keys))) and
+              np.array_equal(out.get("sum", "id")[0], want_sum) and
+              np.array_equal(out.get("max", "x")[0], want_max) and
+              flat.selected == out.selected)
+    ratios = [x / y for x, y in zip(hash_s, flat_s)]
+    row = dict(quals=[repr(q) for q in quals], aggs=[list(x) for x in aggs], by="HashBy(val)",
+               groups_param=1 << 20, distinct_keys=len(keys), selected=out.selected, verified=ok,
+               bytes_read=out.bytes_read, column_bytes=out.column_bytes, groups=out.groups,
+               hashby_ms=[round(x * 1e3, 2) for x in hash_s],
+               no_key_ms=[round(x * 1e3, 2) for x in flat_s],
+               median_ratio_hashby_over_no_key=round(float(np.median(ratios)), 4),
+               hashby_breakdown_s={k: round(v, 4) for k, v in out.seconds.items()},
+               column_GBps=round(out.column_bytes / float(np.median(hash_s)) / 1e9, 2))
+    _log(json.dumps(row))
+    return row
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1 << 27)
@@ -432,6 +498,9 @@ def main(argv=None) -> int:
                     help="add the join rows: a semi-join scan alternated with the same scan "
                          "under isin(), and aggregate(join=, by=) against two projection scans")
     ap.add_argument("--join-pairs", type=int, default=15)
+    ap.add_argument("--hashagg", action="store_true",
+                    help="add the row GROUP BY HashBy(val), a million distinct keys, alternated "
+                         "with the same aggregates without a key (--agg-pairs pairs)")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     import torch
@@ -542,6 +611,8 @@ def main(argv=None) -> int:
             res["agg"] = agg_rows(path, fd, a, col)
         if a.join:
             res["join"] = join_rows(path, fd, a, col)
+        if a.hashagg:
+            res["hashagg"] = hashagg_row(path, fd, a, col)
     finally:
         os.close(fd)
     if a.strings:
@@ -589,7 +660,8 @@ def main(argv=None) -> int:
         res["arrow_scan_GBps"] = min(c["column_GBps"] for c in base_rows)
     res["verified"] = all(c["verified"] for c in res["columns"].values()) and \
         all(r["verified"] for r in res.get("agg", {}).values()) and \
-        all(r["verified"] for r in res.get("join", {}).values())
+        all(r["verified"] for r in res.get("join", {}).values()) and \
+        res.get("hashagg", {}).get("verified", True)
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:

@@ -36,7 +36,8 @@ def main(argv=None):
     ap.add_argument("--only", default="crc,scatter,verify,heap,lz4,snappy,filter",
                     help="also: mvcc (snapshot check), par (LZ4 decoders by stream count), "
                          "agg (aggregate kernels next to column_filter_i64), "
-                         "join (hash-join probe next to column_filter_i64)")
+                         "join (hash-join probe next to column_filter_i64), "
+                         "hashagg (hash GROUP BY next to column_filter_i64 and the LDS path)")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     only = set(a.only.split(","))
@@ -184,6 +185,8 @@ def main(argv=None):
         _agg_rows(n, dev, log, column_filter)
     if "join" in only:
         _join_rows(n, dev, log, column_filter)
+    if "hashagg" in only:
+        _hashagg_rows(n, dev, log, column_filter)
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:
@@ -272,6 +275,82 @@ def _join_rows(n, dev, log, column_filter):
         print(f"column_join table {tag}: {nk} keys, largest displacement {int(hdr[J.H_MAXDISP])}",
               file=sys.stderr, flush=True)
         del fk, table
+
+
+def _hashagg_rows(n, dev, log, column_filter):
+    """Hash GROUP BY (colgroup.hip) on one HBM-resident record batch, every
+    row selected, next to column_filter_i64 and column_agg_i64_sum_by256 (the
+    LDS path) of the same run on the same values.  Per key column: the
+    find-or-insert alone (``codes``: GB/s of the int64 keys read), and codes +
+    accumulate for i64 SUM and for f64 SUM|MIN|MAX (GB/s of the key and value
+    columns, 16 bytes a row; the int32 code buffer in between is not counted).
+    The timed launches run on a table that already holds every key (the
+    warm-up inserted them).  ``_c0`` / ``_c1``: the accumulate launch alone
+    without / with the in-word combining of the first row's code.  Keys:
+    uniform over 256, 64 Ki, 1 Mi and 8 Mi values, a sorted column of 64 Ki
+    values, and one with every other row on one key."""
+    from nvme_strom_amd.ops import colagg as A
+    from nvme_strom_amd.ops import colgroup as G
+    nv = n // 8
+    nwords = (nv + 63) // 64
+    v = torch.randint(-1000, 1000, (nv,), dtype=torch.int64, device=dev)
+    f = torch.rand(nv, dtype=torch.float64, device=dev)
+    log("column_filter_i64", timed(lambda: column_filter(v, -100, 100)), nv * 8)
+
+    def tab(t):
+        return torch.tensor([[t.data_ptr(), 0, nv, 0, 0]], dtype=torch.int64, device=dev)
+    tv, tf = tab(v), tab(f)
+    ones = torch.full((nwords,), -1, dtype=torch.int64, device=dev)
+    if nv % 64:
+        ones[-1] = (1 << (nv % 64)) - 1
+    k32 = torch.randint(0, 255, (nv,), dtype=torch.int32, device=dev)
+    lay = A.Layout([A.Entry(A.SUM, "i8")], 256, 1)
+    block = A.alloc_block(lay, dev)
+    slabs = torch.empty(A.slab_words(lay, 0, nwords), dtype=torch.int64, device=dev)
+    t32 = tab(k32)
+
+    def lds():
+        _, k = A.agg_launch(lay, 0, block, ones, nwords, tv, t32, slabs)
+        A.agg_reduce(lay, 0, block, slabs, k)
+    log("column_agg_i64_sum_by256_sel100", timed(lds), nv * 12)
+    del k32, t32, slabs
+    kbuf = torch.empty(nwords * 64, dtype=torch.int32, device=dev)
+    ctab = tab(kbuf)
+    dst = torch.empty(nwords, dtype=torch.int64, device=dev)
+    ents = [A.Entry(A.SUM, "i8"), A.Entry(A.SUM | A.MIN | A.MAX, "f8")]
+    vals = (tv, tf)
+
+    def keys(tag):
+        if tag == "sorted64Ki":
+            return torch.sort(torch.randint(0, 1 << 16, (nv,), dtype=torch.int64, device=dev))[0]
+        if tag == "skewed64Ki":
+            k = torch.randint(1, 1 << 16, (nv,), dtype=torch.int64, device=dev)
+            k[::2] = 0
+            return k
+        return torch.randint(0, int(tag), (nv,), dtype=torch.int64, device=dev)
+    for tag, d in (("256", 256), ("65536", 1 << 16), ("1048576", 1 << 20), ("8388608", 1 << 23),
+                   ("sorted64Ki", 1 << 16), ("skewed64Ki", 1 << 16)):
+        k = keys(tag)
+        tk = tab(k)
+        t = G.DeviceGroups(ents, d, dev)
+        name = f"uniform{tag}" if tag.isdigit() else tag
+
+        def codes():
+            G.group_codes(t, G.KEY_CODE["i8"], tk, nwords, ones, dst, ctab)
+        log(f"hashagg_codes_{name}", timed(codes, 3), nv * 8)
+        for e, what in enumerate(("i64_sum", "f64_sum_min_max")):
+            def both(e=e):
+                codes()
+                G.group_agg(t, e, dst, nwords, vals[e], ctab)
+            log(f"hashagg_{what}_{name}", timed(both, 3), nv * 16)
+            for c in (0, 1):
+                log(f"hashagg_agg_{what}_{name}_c{c}",
+                    timed(lambda: G.group_agg(t, e, dst, nwords, vals[e], ctab, combine=c), 3),
+                    nv * 12)
+        hdr = t.header()
+        print(f"hashagg {name}: capacity {int(hdr[G.H_CAPACITY])}, {int(hdr[G.H_NKEYS])} keys, "
+              f"{int(hdr[G.H_OVERFLOW])} overflowed rows", file=sys.stderr, flush=True)
+        del k, tk, t
 
 
 def _mvcc_rows(n, dev, log):

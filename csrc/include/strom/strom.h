@@ -745,13 +745,45 @@ int strom_column_join(int type, int how, const uint64_t *d_table, uint64_t capac
  * arrival order); a code outside [0, capacity + 2) is not followed.  combine
  * != 0: in a word of mixed codes the rows that share the first selected row's
  * code (when there are two or more) stay in the wave's registers, as a word of
- * one code does, and are added when that code changes. */
+ * one code does, and are added when that code changes.
+ *
+ * Composite keys (GROUP BY a, b, ...: by=HashBy([a, b]) of ArrowScan.aggregate):
+ * strom_group_codes_multi packs up to STROM_GROUP_MAX_KEYS components into the
+ * one key word and walks the same table.  Component i has a field of `bits`
+ * value bits (1 .. its storage width) at bit `shift`, one bit wider when
+ * `nullable`; the first component's field is the topmost, the fields do not
+ * overlap and bits of the word that no field covers are zero.  A signed value
+ * is stored as v + 2^(bits - 1), an unsigned one as it is, a null as the
+ * field's top bit alone: unsigned order of the word is lexicographic order of
+ * the tuples, each column ascending, nulls after all values.  A row with a
+ * value that does not fit its `bits` (or a null in a component not declared
+ * nullable) is cleared from d_dst, has code 0 written and is counted once, in
+ * header word STROM_GROUP_H_RANGE + i of its first such component i.  The word
+ * STROM_JOIN_EMPTY is a legal key here as well (code capacity + 1, HAS_EMPTY);
+ * the null code `capacity` is never written.  d_keys holds the components'
+ * batch tables back to back (component i: d_keys[i * nbatches ..]), all of the
+ * same batches; a component's values may be the int32 buffers of d_codes
+ * themselves (a row's components are read before its code is stored).
+ * Everything else as strom_group_codes, which it leaves alone. */
 #define STROM_GROUP_HDR_WORDS 8
 #define STROM_GROUP_MAX_CAPACITY (1ull << 25)
 #define STROM_GROUP_H_CAPACITY 0
 #define STROM_GROUP_H_NKEYS 1
 #define STROM_GROUP_H_OVERFLOW 2
 #define STROM_GROUP_H_HAS_EMPTY 3
+#define STROM_GROUP_H_RANGE 4           /* words 4 .. 7: one per component */
+#define STROM_GROUP_MAX_KEYS 4
+struct strom_group_key {
+  uint32_t type;                /* STROM_COL_I8 .. U64: how the values are stored */
+  uint32_t bits;                /* value bits of the field */
+  uint32_t shift;               /* the field's lowest bit in the key word */
+  uint32_t nullable;            /* 1: one more bit on top, set for a null */
+};
+struct strom_group_keys {
+  uint32_t nkeys;
+  uint32_t reserved;
+  struct strom_group_key k[STROM_GROUP_MAX_KEYS];
+};
 uint64_t strom_group_capacity(uint64_t groups);
 int strom_group_init(uint64_t *d_table, uint64_t capacity, const struct strom_agg_entry *e,
                      uint32_t n, void *stream);
@@ -759,6 +791,10 @@ int strom_group_codes(int type, uint64_t *d_table, uint64_t capacity,
                       const struct strom_filter_batch *d_keys, uint32_t nbatches, uint64_t nwords,
                       const uint64_t *d_src, uint64_t *d_dst,
                       const struct strom_filter_batch *d_codes, void *stream);
+int strom_group_codes_multi(struct strom_group_keys keys, uint64_t *d_table, uint64_t capacity,
+                            const struct strom_filter_batch *d_keys, uint32_t nbatches,
+                            uint64_t nwords, const uint64_t *d_src, uint64_t *d_dst,
+                            const struct strom_filter_batch *d_codes, void *stream);
 int strom_group_agg(int type, uint32_t ops, const uint64_t *d_bitmap, uint64_t nwords,
                     const struct strom_filter_batch *d_vals,
                     const struct strom_filter_batch *d_codes, uint32_t nbatches, uint64_t *d_acc,

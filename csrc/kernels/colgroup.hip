@@ -16,7 +16,9 @@
 // first compare.  A plain load that still sees a slot free is settled by the
 // CAS (a key word changes once, from free to its key, so a stale load can
 // only say "free").  The row's code goes to an int32 buffer that the
-// accumulate launches read as their key column.
+// accumulate launches read as their key column.  GROUP BY a, b, ... takes the
+// same walk (group_codes_multi_kernel): each lane packs its row's components
+// into one key word first.
 //
 // Accumulate: the walk of agg_keyed_kernel with the accumulators in HBM,
 // updated with device-scope atomics (u64 add / min / max, f64 add).  There
@@ -226,6 +228,182 @@ int launch_codes(uint64_t *table, uint64_t capacity, const strom_filter_batch *k
   const uint32_t grid = (uint32_t)(g > kMaxGrid ? kMaxGrid : (g ? g : 1));
   hipLaunchKernelGGL(group_codes_kernel<T>, dim3(grid), dim3(256), 0, st, table, capacity, kt, nb,
                      nwords, src, dst, ct);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+// ------------------------------------------------- codes, composite keys
+// Up to STROM_GROUP_MAX_KEYS components packed into the one key word of the
+// table above (strom.h: component i's field is bits (+ 1 when nullable) wide
+// at `shift`, the first component in the most significant used bits, a signed
+// value stored as v + 2^(bits - 1), a null as the field's top bit alone).
+// Unsigned order of the word is lexicographic order of the tuples, so the
+// table, its single CAS and everything behind it stay as they are.
+
+// the value at row i of a column of storage type `type`, by value (signed
+// types sign-extended).  `type` is a kernel argument: the switch is uniform.
+__device__ __forceinline__ uint64_t load_wide(uint32_t type, const void *p, uint64_t i) {
+  switch (type) {
+    case STROM_COL_I8: return (uint64_t)(int64_t)((const int8_t *)p)[i];
+    case STROM_COL_I16: return (uint64_t)(int64_t)((const int16_t *)p)[i];
+    case STROM_COL_I32: return (uint64_t)(int64_t)((const int32_t *)p)[i];
+    case STROM_COL_U8: return ((const uint8_t *)p)[i];
+    case STROM_COL_U16: return ((const uint16_t *)p)[i];
+    case STROM_COL_U32: return ((const uint32_t *)p)[i];
+    default: return ((const uint64_t *)p)[i];          // I64, U64
+  }
+}
+
+__host__ __device__ __forceinline__ bool key_signed(uint32_t type) {
+  return type == STROM_COL_I8 || type == STROM_COL_I16 || type == STROM_COL_I32 ||
+         type == STROM_COL_I64;
+}
+
+template <int NK>
+__global__ __launch_bounds__(256) void group_codes_multi_kernel(
+    strom_group_keys ks, uint64_t *table, uint64_t capacity,
+    const strom_filter_batch *__restrict__ kt, uint32_t nb, uint64_t nwords, const uint64_t *src,
+    uint64_t *dst, const strom_filter_batch *__restrict__ ct) {
+  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const uint64_t mask = capacity - 1;
+  uint64_t *slots = table + kHdr;
+  uint32_t nins = 0, nover = 0, nrange[NK];           // wave-uniform
+#pragma unroll
+  for (int i = 0; i < NK; ++i) nrange[i] = 0;
+  const uint64_t step = (uint64_t)gridDim.x * 4 * kU;
+  for (uint64_t w0 = ((uint64_t)blockIdx.x * 4 + wid) * kU; w0 < nwords; w0 += step) {
+    uint64_t raw[kU], sel[kU], key[kU], at[kU], bk[kU], e[kU];
+    uint32_t bi[kU];
+    int32_t bad[kU];                // the first component that does not fit, or -1
+    bool act[kU];
+    int32_t code[kU];
+    // pass 1: the source word, every component's value (read before any code
+    // is stored: a component may live in the code buffer), the packed key,
+    // the home slot's load
+#pragma unroll
+    for (uint32_t u = 0; u < kU; ++u) {
+      const uint64_t w = w0 + u;
+      raw[u] = 0;
+      sel[u] = 0;
+      key[u] = 0;
+      at[u] = 0;
+      bk[u] = 0;
+      bi[u] = 0;
+      bad[u] = -1;
+      act[u] = false;
+      code[u] = 0;
+      e[u] = kEmpty;
+      if (w >= nwords) continue;
+      const uint64_t word = src[w];                    // uniform load, one per wave
+      if (!word) continue;
+      raw[u] = word;
+      // the components' tables describe the same batches: one search
+      bi[u] = batch_of(kt, nb, w);
+      const strom_filter_batch &b0 = kt[bi[u]];
+      bk[u] = w - b0.word_base;
+      sel[u] = word & row_mask(b0, bk[u]);
+      if (!((sel[u] >> lane) & 1)) continue;
+      uint64_t packed = 0;
+#pragma unroll
+      for (int i = 0; i < NK; ++i) {
+        const strom_group_key &kd = ks.k[i];
+        const strom_filter_batch &b = kt[(uint64_t)i * nb + bi[u]];
+        uint64_t f;
+        bool fits;
+        if (b.valid && !((((const uint64_t *)b.valid)[bk[u]] >> lane) & 1)) {
+          // a null where none was declared has no field value
+          fits = kd.nullable != 0;
+          f = 1ull << (kd.bits & 63);
+        } else {
+          f = load_wide(kd.type, (const void *)b.values, bk[u] * 64 + lane);
+          if (key_signed(kd.type)) f += 1ull << (kd.bits - 1);
+          fits = kd.bits >= 64 || !(f >> kd.bits);
+        }
+        if (!fits && bad[u] < 0) bad[u] = i;
+        packed |= f << kd.shift;
+      }
+      if (bad[u] >= 0) continue;                       // no code; cleared in pass 2
+      key[u] = packed;
+      if (key[u] == kEmpty) {
+        // the one key the slots cannot hold: a flag in the header
+        code[u] = (int32_t)(capacity + 1);
+        if (!table[STROM_GROUP_H_HAS_EMPTY] &&
+            atomicCAS((ull *)&table[STROM_GROUP_H_HAS_EMPTY], 0ull, 1ull) == 0ull)
+          atomicAdd((ull *)&table[STROM_GROUP_H_NKEYS], 1ull);      // once per table
+        continue;
+      }
+      act[u] = true;
+      at[u] = fmix64(key[u]) & mask;
+      e[u] = slots[at[u]];
+    }
+    // pass 2: compare, claim a free slot, walk on while it holds another key
+#pragma unroll
+    for (uint32_t u = 0; u < kU; ++u) {
+      const uint64_t w = w0 + u;
+      if (w >= nwords) break;
+      uint64_t word = sel[u];
+      if (sel[u]) {
+        bool go = act[u], ins = false, over = false;
+        // at most `capacity` slots are looked at, whatever the arguments
+        for (uint64_t d = 0;; ++d) {
+          if (go) {
+            uint64_t cur = e[u];
+            if (cur == kEmpty) {
+              cur = atomicCAS((ull *)&slots[at[u]], (ull)kEmpty, (ull)key[u]);
+              if (cur == kEmpty) {
+                ins = true;
+                cur = key[u];
+              }
+            }
+            if (cur == key[u]) {
+              code[u] = (int32_t)at[u];
+              go = false;
+            } else if (d + 1 >= capacity) {
+              over = true;
+              go = false;
+            }
+          }
+          if (!__ballot(go)) break;
+          if (go) {
+            at[u] = (at[u] + 1) & mask;
+            e[u] = slots[at[u]];
+          }
+        }
+        nins += __popcll(__ballot(ins));
+        const uint64_t om = __ballot(over);
+        nover += __popcll(om);
+        word &= ~om;                                   // no code: not accumulated
+#pragma unroll
+        for (int i = 0; i < NK; ++i) {
+          const uint64_t rm = __ballot(bad[u] == i);
+          nrange[i] += __popcll(rm);
+          word &= ~rm;
+        }
+        if ((sel[u] >> lane) & 1)
+          ((int32_t *)ct[bi[u]].values)[bk[u] * 64 + lane] = code[u];
+      }
+      // in place, a word that stays as it is (a zero one above all) is not stored
+      if (lane == 0 && (dst != src || word != raw[u])) dst[w] = word;
+    }
+  }
+  // the counters once per wave
+  if (lane == 0) {
+    if (nins) atomicAdd((ull *)&table[STROM_GROUP_H_NKEYS], (ull)nins);
+    if (nover) atomicAdd((ull *)&table[STROM_GROUP_H_OVERFLOW], (ull)nover);
+#pragma unroll
+    for (int i = 0; i < NK; ++i)
+      if (nrange[i]) atomicAdd((ull *)&table[STROM_GROUP_H_RANGE + i], (ull)nrange[i]);
+  }
+}
+
+template <int NK>
+int launch_codes_multi(const strom_group_keys &ks, uint64_t *table, uint64_t capacity,
+                       const strom_filter_batch *kt, uint32_t nb, uint64_t nwords,
+                       const uint64_t *src, uint64_t *dst, const strom_filter_batch *ct,
+                       hipStream_t st) {
+  const uint64_t g = (nwords + 4 * kU - 1) / (4 * kU);
+  const uint32_t grid = (uint32_t)(g > kMaxGrid ? kMaxGrid : (g ? g : 1));
+  hipLaunchKernelGGL(group_codes_multi_kernel<NK>, dim3(grid), dim3(256), 0, st, ks, table,
+                     capacity, kt, nb, nwords, src, dst, ct);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
@@ -495,6 +673,57 @@ extern "C" int strom_group_codes(int type, uint64_t *d_table, uint64_t capacity,
     default: return -22;        // floats, strings, bool, decimal: no integer key
   }
 #undef CODES
+}
+
+namespace {
+
+uint32_t key_storage_bits(uint32_t type) {
+  switch (type) {
+    case STROM_COL_I8: case STROM_COL_U8: return 8;
+    case STROM_COL_I16: case STROM_COL_U16: return 16;
+    case STROM_COL_I32: case STROM_COL_U32: return 32;
+    case STROM_COL_I64: case STROM_COL_U64: return 64;
+    default: return 0;          // floats, strings, bool, decimal: no integer key
+  }
+}
+
+// fields inside the word, the first component on top, none overlapping
+bool keys_ok(const strom_group_keys &ks) {
+  if (ks.nkeys < 1 || ks.nkeys > STROM_GROUP_MAX_KEYS) return false;
+  uint32_t top = 64;            // the bits below `top` are still free
+  for (uint32_t i = 0; i < ks.nkeys; ++i) {
+    const strom_group_key &k = ks.k[i];
+    const uint32_t sb = key_storage_bits(k.type);
+    if (!sb || k.bits < 1 || k.bits > sb || k.nullable > 1) return false;
+    const uint32_t width = k.bits + k.nullable;
+    if (width > 64 || k.shift > 64 - width || k.shift + width > top) return false;
+    top = k.shift;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" int strom_group_codes_multi(struct strom_group_keys keys, uint64_t *d_table,
+                                       uint64_t capacity, const strom_filter_batch *d_keys,
+                                       uint32_t nbatches, uint64_t nwords, const uint64_t *d_src,
+                                       uint64_t *d_dst, const strom_filter_batch *d_codes,
+                                       void *stream) {
+  if (!d_table || ((uintptr_t)d_table & 7) || !cap_ok(capacity) || !keys_ok(keys)) return -22;
+  if (!d_keys || !d_codes || !nbatches || !d_src || !d_dst || ((uintptr_t)d_src & 7) ||
+      ((uintptr_t)d_dst & 7))
+    return -22;
+  if (!nwords) return 0;
+  hipStream_t st = (hipStream_t)stream;
+#define CODESN(N) launch_codes_multi<N>(keys, d_table, capacity, d_keys, nbatches, nwords, d_src, \
+                                        d_dst, d_codes, st)
+  switch (keys.nkeys) {
+    case 1: return CODESN(1);
+    case 2: return CODESN(2);
+    case 3: return CODESN(3);
+    default: return CODESN(4);
+  }
+#undef CODESN
 }
 
 extern "C" int strom_group_agg(int type, uint32_t ops, const uint64_t *d_bitmap, uint64_t nwords,

@@ -192,6 +192,17 @@ class DecompDesc(C.Structure):
                 ("dst_len", C.c_uint32)]
 
 
+class GroupKey(C.Structure):
+    """strom_group_key: one component of a composite GROUP BY key."""
+    _fields_ = [("type", C.c_uint32), ("bits", C.c_uint32), ("shift", C.c_uint32),
+                ("nullable", C.c_uint32)]
+
+
+class GroupKeys(C.Structure):
+    """strom_group_keys, passed by value to strom_group_codes_multi."""
+    _fields_ = [("nkeys", C.c_uint32), ("reserved", C.c_uint32), ("k", GroupKey * 4)]
+
+
 # ----------------------------------------------------------------- loading
 _lib = None
 _lock = threading.Lock()
@@ -334,6 +345,9 @@ _SIGS = {
     "strom_group_init": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "strom_group_codes": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                     C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "strom_group_codes_multi": (C.c_int, [GroupKeys, C.c_void_p, C.c_uint64, C.c_void_p,
+                                          C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
     "strom_group_agg": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
                                   C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int,
                                   C.c_void_p]),

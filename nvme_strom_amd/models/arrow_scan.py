@@ -203,13 +203,63 @@ class HashBy:
     in LDS that ``by="name"`` uses.  ``groups``: the largest number of
     distinct non-null keys the scan may meet, 1 <= groups <= 2^24; the table
     gets the next power of two >= 2 * groups slots and is not grown: a scan
-    that meets more keys raises RuntimeError at its one sync."""
+    that meets more keys raises RuntimeError at its one sync.
 
-    def __init__(self, col: str, groups: int = 1 << 16):
-        self.col = str(col)
+    ``HashBy(["region", "day"], groups)`` — a list or tuple, also of one — is
+    ``GROUP BY region, day``: up to four components, each such a column or
+    one attribute of the scan's semi-join (``dim["category"]``), packed into
+    the table's one 64-bit key word (ops/colgroup.KeySpec).  A column takes
+    its storage width, one bit more when any record batch of the file has
+    nulls in it; an attribute takes ceil(log2(number of its values)) bits.
+    All widths together must fit 64 bits: ``bits={"col": n}`` declares that
+    ``col``'s values lie in [-2^(n-1), 2^(n-1)) (signed) or [0, 2^n); a
+    selected row outside that range raises RuntimeError at the sync.
+    ``groups`` counts distinct tuples.  Rows come back in lexicographic
+    order, each column ascending, nulls last (an attribute by its code)."""
+
+    def __init__(self, col, groups: int = 1 << 16, bits: Optional[dict] = None):
         self.groups = G.check_groups(groups)
+        self.comps: Optional[list] = None
+        self.bits: Dict[str, int] = {}
+        if isinstance(col, (list, tuple)):
+            comps = list(col)
+            if not comps:
+                raise ValueError("HashBy: an empty list of key columns")
+            if len(comps) > G.MAX_KEYS:
+                raise NotImplementedError(f"HashBy of {len(comps)} components: at most "
+                                          f"{G.MAX_KEYS} are packed into the 64-bit key")
+            comps = [c if isinstance(c, JoinAttr) else str(c) for c in comps]
+            names = [("attr", id(c.table), c.name) if isinstance(c, JoinAttr) else ("col", c)
+                     for c in comps]
+            for n in names:
+                if names.count(n) > 1:
+                    raise ValueError(f"HashBy: {n[-1]!r} appears twice")
+            if sum(isinstance(c, JoinAttr) for c in comps) > 1:
+                raise NotImplementedError("HashBy: one JoinTable attribute per key (the probe "
+                                          "writes one attribute's codes)")
+            cols = [c for c in comps if not isinstance(c, JoinAttr)]
+            for n, b in (bits or {}).items():
+                if n not in cols:
+                    raise ValueError(f"bits= names {n!r}, which is not a column of the key")
+                if isinstance(b, bool) or int(b) != b or not 1 <= int(b) <= 64:
+                    raise ValueError(f"bits={b!r} for {n}: 1 <= bits <= its storage width")
+                self.bits[n] = int(b)
+            self.comps = comps
+            self.col = tuple(c.name if isinstance(c, JoinAttr) else c for c in comps)
+        else:
+            if bits:
+                raise ValueError("bits= belongs to a list of key columns")
+            self.col = str(col)
+
+    @property
+    def attr(self) -> Optional[JoinAttr]:
+        """The JoinTable attribute among the components, if any."""
+        return next((c for c in self.comps or [] if isinstance(c, JoinAttr)), None)
 
     def __repr__(self) -> str:
+        if self.comps is not None:
+            return f"HashBy({self.comps!r}, groups={self.groups}" + \
+                (f", bits={self.bits}" if self.bits else "") + ")"
         return f"HashBy({self.col!r}, groups={self.groups})"
 
 
@@ -274,6 +324,9 @@ class _HashRun:
     col: int                      # plan column of the key
     code: int                     # its STROM_COL_* storage type
     dev: G.DeviceGroups
+    # a composite key (dev.spec): the plan column of each component, None for
+    # the join attribute, whose codes the probe leaves in the slot's key buffer
+    cols: Optional[List[Optional[int]]] = None
 
 
 @dataclass
@@ -986,17 +1039,31 @@ class ArrowScan:
                 if s.keybuf is None or s.keybuf.numel() < s.bitmap.numel() * 64:
                     s.keybuf = torch.empty(s.bitmap.numel() * 64, dtype=torch.int32,
                                            device=self.device)
-                key5 = (tabs_np[hs.col] if hs.col in tabs_np else
-                        self._pointers(g, hs.col, base, dec_base))[:, :BATCH_FIELDS]
-                c5 = key5.copy()
+                c5 = g.table[:, :BATCH_FIELDS].copy()
                 c5[:, 0] = s.keybuf.data_ptr() + g.table[:, 3] * 256
                 c5[:, 1] = 0
-                d_h = self._upload(s, np.stack([key5, c5]))
-                s.keep.append(d_h)
-                G.group_codes(hs.dev, hs.code, d_h[0], g.words, bitmap, s.bitmap, d_h[1],
-                              stream=cs)
+                if hs.cols is not None:
+                    # a composite key: every component's table, the join
+                    # attribute's being the code buffers' own (the launch runs
+                    # in place there: a lane reads its row's components before
+                    # it stores the row's code), then the code buffers'
+                    k5 = [c5 if c is None else
+                          (tabs_np[c] if c in tabs_np else
+                           self._pointers(g, c, base, dec_base))[:, :BATCH_FIELDS]
+                          for c in hs.cols]
+                    d_h = self._upload(s, np.stack(k5 + [c5]))
+                    s.keep.append(d_h)
+                    G.group_codes_multi(hs.dev, d_h[:-1], g.words, bitmap, s.bitmap, d_h[-1],
+                                        stream=cs)
+                else:
+                    key5 = (tabs_np[hs.col] if hs.col in tabs_np else
+                            self._pointers(g, hs.col, base, dec_base))[:, :BATCH_FIELDS]
+                    d_h = self._upload(s, np.stack([key5, c5]))
+                    s.keep.append(d_h)
+                    G.group_codes(hs.dev, hs.code, d_h[0], g.words, bitmap, s.bitmap, d_h[1],
+                                  stream=cs)
                 bitmap = s.bitmap
-                kout_ptr = d_h[1].data_ptr()
+                kout_ptr = d_h[-1].data_ptr()
             state["marks"].append((k, "quals_queued", time.perf_counter()))
             # emit tables: the strom_filter_batch prefix of the qual tables
             any_col = spec[0][0][0] if spec else (jn.col if jn is not None else 0)
@@ -1268,7 +1335,12 @@ class ArrowScan:
         rows come back ascending by key, the null group last, and float sums
         are not bitwise reproducible from run to run (the keyed LDS path's are
         not either).  More than ``groups`` distinct keys raise RuntimeError at
-        the scan's sync; there is no retry.  ``join=`` as in scan_where: only the
+        the scan's sync; there is no retry.  ``HashBy([a, b, ...])`` groups by
+        up to four such columns (or one attribute of the semi-join among
+        them) packed into the table's key word: ``AggOut.keys`` are tuples in
+        lexicographic order, nulls last per column, ``AggOut.key_columns``
+        the same as arrays; a selected value outside a declared ``bits=``
+        raises RuntimeError at the sync.  ``join=`` as in scan_where: only the
         joined rows are aggregated, and ``by=dim[attr]`` groups them by an
         attribute of the JoinTable — the probe writes each row's attribute
         code into the slot's key buffer and the aggregate kernels take it as
@@ -1276,7 +1348,7 @@ class ArrowScan:
         t0 = time.perf_counter()
         battr = by if isinstance(by, JoinAttr) else None
         hb = by if isinstance(by, HashBy) else None
-        join = _check_join(self.meta, join, battr)
+        join = _check_join(self.meta, join, battr if hb is None else hb.attr)
         if battr is not None or hb is not None:
             by = None
         cl = clauses(quals) if quals else []
@@ -1304,7 +1376,8 @@ class ArrowScan:
         spec = [[(names.index(p.col), self._compile(p)) for p in c] for c in cl]
         t_plan = time.perf_counter()
         if hb is not None and (not groups or nrows == 0):
-            return _hash_out(agg, G.empty_groups(agg.layout.entries, agg.hash_unsigned), nrows,
+            return _hash_out(agg, G.empty_groups(agg.layout.entries, agg.hash_unsigned,
+                                                 agg.keyspec), nrows,
                              {"total_s": time.perf_counter() - t0})
         if not groups or nrows == 0:
             return _agg_out(agg, A.new_block(agg.layout), nrows,
@@ -1324,12 +1397,16 @@ class ArrowScan:
                 # the table and its accumulators, initialised before any
                 # launch can see a slot (block_ready below)
                 dev = G.DeviceGroups(agg.layout.entries, hb.groups, self.device,
-                                     agg.hash_unsigned, stream=self.emit_stream)
+                                     agg.hash_unsigned, stream=self.emit_stream,
+                                     spec=agg.keyspec)
         state = dict(agg=agg, block=block, count=z(), err=z(), wait_s=0.0, bytes_read=0,
                      column_bytes=0, marks=[])
         if join is not None:
-            state["join"] = self._join_run(join, names, battr)
-        if hb is not None:
+            state["join"] = self._join_run(join, names, battr if hb is None else hb.attr)
+        if agg.keyspec is not None:
+            state["hash"] = _HashRun(-1, 0, dev, [None if isinstance(c, JoinAttr) else
+                                                  names.index(c) for c in hb.comps])
+        elif hb is not None:
             kc = self.meta.schema[self.meta.column_index(hb.col)]
             state["hash"] = _HashRun(names.index(hb.col), G.KEY_CODE[kc.storage], dev)
         # the aggregate launches (slot streams) count malformed keys in the
@@ -1371,6 +1448,8 @@ class ArrowScan:
                     f"the table is full ({nk} keys in it, {over} selected row(s) found no slot)"
                 raise RuntimeError(f"GROUP BY HashBy({hb.col!r}): more than groups={hb.groups} "
                                    f"distinct keys: {seen}; scan again with a larger groups=")
+            if agg.keyspec is not None:
+                _check_range(agg.keyspec, hdr[G.H_RANGE:G.H_RANGE + len(agg.keyspec)])
             return _hash_out(agg, found, nrows, secs, bytes_read=state["bytes_read"],
                              column_bytes=state["column_bytes"], groups=len(groups))
         return _agg_out(agg, host, nrows,
@@ -1559,6 +1638,49 @@ class _AggSpec:
     join_attr: bool = False                 # ``by`` names a JoinTable attribute
     hashed: bool = False                    # by=HashBy(by): layout / keyvals per result
     hash_unsigned: bool = False             # its keys are uint64
+    keyspec: Optional[G.KeySpec] = None     # by=HashBy([...]): how the components are packed
+    key_attrs: Optional[list] = None        # per component: a join attribute's values, or None
+
+
+def _check_range(spec: G.KeySpec, misfit) -> None:
+    """Raise for selected rows that a component's declared width could not
+    hold (they were left out of every group)."""
+    for c, n in zip(spec.comps, np.asarray(misfit).tolist()):
+        if n:
+            what = f"declared bits={c.bits}" + ("" if c.nullable else ", no nulls")
+            raise RuntimeError(f"GROUP BY key component {c.name} ({what}): {int(n)} selected "
+                               "row(s) with a value outside that range; scan again with a larger "
+                               f"bits={{{c.name!r}: n}}")
+
+
+def _key_spec(meta: ArrowFile, hb: HashBy) -> Tuple[G.KeySpec, list]:
+    """The KeySpec of by=HashBy([...]) against the schema, and per component
+    its join attribute's values (None for a column).  A column is nullable if
+    any record batch of the file has nulls in it — the whole file, whatever
+    range is scanned, so that results of its ranges pack alike and merge."""
+    schema = {c.name: (i, c) for i, c in enumerate(meta.schema)}
+    comps, attrs = [], []
+    for c in hb.comps:
+        if isinstance(c, JoinAttr):
+            nv = max(len(c.values), 1)
+            # codes 0 .. nv - 1, never negative: an unsigned field over the
+            # probe's int32 buffer
+            comps.append((c.name, "u4", max(1, int(nv - 1).bit_length()), False))
+            attrs.append(list(c.values))
+            continue
+        if c not in schema:
+            raise ValueError(f"no column {c!r}")
+        ci, k = schema[c]
+        if k.dictionary is not None or k.kind not in ("int",) + _TEMPORAL or \
+                k.storage not in G.KEY_CODE:
+            kind = "dictionary-encoded" if k.dictionary is not None else k.kind
+            raise NotImplementedError(
+                f"GROUP BY HashBy(..., {c}, ...): {kind} keys (integer and date / time / "
+                "timestamp / duration columns are hashed)")
+        nullable = bool(meta.nbatches) and bool(np.any(np.asarray(meta.columns[ci].null_count)))
+        comps.append((c, k.storage, hb.bits.get(c), nullable))
+        attrs.append(None)
+    return G.KeySpec(comps), attrs
 
 
 def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary,
@@ -1620,7 +1742,12 @@ def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary,
                 "columns are grouped on the GPU by name; by=HashBy(column) groups an integer "
                 "or temporal column of any width)")
         nslots = len(keyvals) + 1
-    if hb is not None:
+    keyspec = key_attrs = None
+    if hb is not None and hb.comps is not None:
+        if jattr is not None:
+            raise ValueError("by=: a JoinTable attribute or HashBy, not both")
+        keyspec, key_attrs = _key_spec(meta, hb)
+    elif hb is not None:
         if jattr is not None:
             raise ValueError("by=: a JoinTable attribute or HashBy, not both")
         if hb.col not in schema:
@@ -1646,6 +1773,13 @@ def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary,
     names = [n for n in entry_names[1:]]
     if by is not None and by not in names:
         names.append(by)
+    if keyspec is not None:
+        for c in hb.comps:
+            if not isinstance(c, JoinAttr) and c not in names:
+                names.append(c)
+        return _AggSpec(aggs, hb.col, A.Layout(entries), entry_names, names,
+                        {n: schema[n] for n in names}, None, hashed=True, hash_unsigned=True,
+                        keyspec=keyspec, key_attrs=key_attrs)
     if hb is not None:
         if hb.col not in names:
             names.append(hb.col)
@@ -1686,6 +1820,11 @@ class AggOut:
     _spec: Optional[_AggSpec] = None
     _block: Optional[np.ndarray] = None
     _found: Optional[G.Groups] = None       # by=HashBy: key -> accumulators
+    # by=HashBy([...]): per component (values, valid) over the rows of the
+    # result — a column's values in its storage dtype (ticks for temporal
+    # ones), an attribute's as objects; ``keys`` are then tuples of them with
+    # None for a null.  None for every other by=
+    key_columns: Optional[List[Tuple[np.ndarray, np.ndarray]]] = None
 
     def get(self, fn: str, col: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray]:
         """(values, valid) of one requested aggregate."""
@@ -1704,6 +1843,9 @@ class AggOut:
                 raise ValueError("merge: a HashBy result merges with HashBy results only")
             if a.aggs != b.aggs or a.by != b.by or a.hash_unsigned != b.hash_unsigned:
                 raise ValueError("merge: different aggregates or HashBy column")
+            if a.keyspec != b.keyspec or a.key_attrs != b.key_attrs:
+                raise ValueError(f"merge: composite keys packed differently ({a.keyspec} and "
+                                 f"{b.keyspec}) or other attribute values")
             return _hash_out(a, G.merge(self._found, other._found), self.rows + other.rows, secs,
                              bytes_read=self.bytes_read + other.bytes_read,
                              column_bytes=self.column_bytes + other.column_bytes,
@@ -1770,6 +1912,40 @@ def _hash_out(spec: _AggSpec, found: G.Groups, rows: int, seconds: Dict[str, flo
     per = replace(spec, layout=found.layout, keyvals=found.keys)
     out = _agg_out(per, found.block, rows, seconds, **kw)
     out._found = found
+    if spec.keyspec is not None:
+        # the packed words (ascending: lexicographic) back into components;
+        # the null keys' slot is never used on this path.  Possibly millions
+        # of groups: numpy per component, Python only for the tuples
+        count = A.entry_arrays(found.layout, found.block, 0)["count"][:-1]
+        vals, oks = spec.keyspec.unpack(found.keys[count > 0])
+        cols, lists = [], []
+        for v, ok, attr in zip(vals, oks, spec.key_attrs):
+            if attr is not None:
+                # a code's value; None is a value of the attribute like any other
+                table = np.empty(len(attr) + 1, object)
+                table[:len(attr)] = attr
+                v = table[np.minimum(v.astype(np.int64), len(attr))]
+                ok = np.array([x is not None for x in attr] + [False], bool)[
+                    np.minimum(vals[len(cols)].astype(np.int64), len(attr))]
+                lists.append(v.tolist())
+            elif ok.all():
+                lists.append(v.tolist())
+            else:
+                o = v.astype(object)
+                o[~ok] = None
+                lists.append(o.tolist())
+            cols.append((v, ok))
+        # a million tuples: the cyclic collector would walk them again and
+        # again while the list grows (half the time of this step)
+        import gc
+        paused = gc.isenabled()
+        gc.disable()
+        try:
+            out.keys = list(zip(*lists)) if len(count) else []
+        finally:
+            if paused:
+                gc.enable()
+        out.key_columns = cols
     return out
 
 
@@ -1792,11 +1968,14 @@ def host_aggregate(path: str, quals, aggs, by=None,
         return dicts[name]
     battr = by if isinstance(by, JoinAttr) else None
     hb = by if isinstance(by, HashBy) else None
-    join = _check_join(meta, join, battr)
+    hattr = hb.attr if hb is not None else None
+    join = _check_join(meta, join, battr if hb is None else hattr)
     if battr is not None or hb is not None:
         by = None
     spec = _agg_spec(meta, aggs, by, dictionary, battr, hb)
-    found = G.empty_groups(spec.layout.entries, spec.hash_unsigned) if hb is not None else None
+    found = G.empty_groups(spec.layout.entries, spec.hash_unsigned, spec.keyspec) \
+        if hb is not None else None
+    misfit = np.zeros(G.MAX_KEYS, np.int64)
     comp = []
     for c in cl:
         row = []
@@ -1826,7 +2005,8 @@ def host_aggregate(path: str, quals, aggs, by=None,
                 vraw = read_buffer(src, ch.validity, b.codec) if ch.null_count else b""
                 ok = validity_bits(vraw, ch.length)
                 if not any(n == q for c in comp for q, _ in c) and n != by and \
-                        not (join and n == join.col) and not (hb and n == hb.col) and \
+                        not (join and n == join.col) and \
+                        not (hb and (n == hb.col or n in (hb.comps or ()))) and \
                         lay.entries[spec.entry_names.index(n)].dtype is None:
                     data[n] = (None, ok)          # counted only: its validity is enough
                     continue
@@ -1857,6 +2037,22 @@ def host_aggregate(path: str, quals, aggs, by=None,
                 if kv.dtype == np.int8 and schema[by][1].dictionary is None:
                     kv = kv.view(np.uint8)        # 8-bit key: the slot is the byte
                 key = (kv, kok)
+            ecols = [(None, None) if name is None else data[name] for name in spec.entry_names]
+            if spec.keyspec is not None:
+                # the composite path's twin: packed by the same KeySpec
+                kcols, koks = [], []
+                for c in hb.comps:
+                    if isinstance(c, JoinAttr):
+                        kcols.append(np.where(m, c.codes[jrow] if len(c.codes) else 0, 0)
+                                     .astype(np.uint32))
+                        koks.append(None)
+                    else:
+                        kcols.append(np.asarray(data[c][0]))
+                        koks.append(data[c][1])
+                part, bad = G.host_group_agg_multi(lay.entries, m, spec.keyspec, kcols, koks, ecols)
+                found = G.merge(found, part)
+                misfit[:len(bad)] += bad
+                continue
             if hb is not None:
                 # the hash path's twin: this batch's groups, united by key
                 kv, kok = data[hb.col]
@@ -1874,5 +2070,7 @@ def host_aggregate(path: str, quals, aggs, by=None,
             raise RuntimeError(f"GROUP BY HashBy({hb.col!r}): more than groups={hb.groups} "
                                f"distinct keys: {len(found.keys)} distinct keys seen; scan again "
                                "with a larger groups=")
+        if spec.keyspec is not None:
+            _check_range(spec.keyspec, misfit[:len(spec.keyspec)])
         return _hash_out(spec, found, nrows, {"total_s": time.perf_counter() - t0})
     return _agg_out(spec, block, nrows, {"total_s": time.perf_counter() - t0})

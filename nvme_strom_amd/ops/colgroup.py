@@ -15,6 +15,13 @@ uint64 for an unsigned column) and a colagg block (ops/colagg.py: the same
 words, the same encodings) of ``len(keys) + 1`` slots, the last one the null
 keys' group.  ``merge`` unites two of them by key.
 
+GROUP BY several columns (``KeySpec``, ``group_codes_multi``,
+``host_group_agg_multi``): the components are packed into the one key word,
+so that unsigned order of the words is lexicographic order of the tuples;
+everything above then holds with uint64 keys, and ``Groups.spec`` says how to
+take them apart again.  A null component is a bit of the word: the null
+keys' slot stays empty on that path.
+
 Semantics are colagg's; float sums are added with global atomics on the
 device, in the order the rows arrive: they are not bitwise reproducible from
 run to run (the LDS path's keyed float sums are not either).
@@ -23,7 +30,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 
@@ -86,14 +93,160 @@ def wide_keys(values) -> np.ndarray:
     return v.astype(np.uint64 if v.dtype.kind == "u" else np.int64)
 
 
+# ------------------------------------------------------------ composite keys
+MAX_KEYS = 4
+H_RANGE = 4                               # header words 4 .. 7: rows a component did not fit
+
+
+@dataclass(frozen=True)
+class KeyComp:
+    """One component of a composite key: ``storage`` how its values are
+    stored ("i1" .. "u8"), ``bits`` the value bits of its field, ``nullable``
+    one more bit on top for a null, ``shift`` the field's lowest bit."""
+    name: str
+    storage: str
+    bits: int
+    nullable: bool
+    shift: int
+
+    @property
+    def width(self) -> int:
+        return self.bits + int(self.nullable)
+
+    @property
+    def signed(self) -> bool:
+        return self.storage[0] == "i"
+
+
+class KeySpec:
+    """How the components of ``GROUP BY a, b, ...`` share the table's one
+    64-bit key word (strom.h, strom_group_codes_multi): the first component
+    in the most significant used bits, a signed value biased by
+    2^(bits - 1), a null as the field's top bit alone — unsigned order of
+    the word is lexicographic order of the tuples, nulls after all values.
+    The kernel and the numpy twin both pack by this object, so they agree
+    key by key.
+
+    ``comps``: (name, storage, bits or None, nullable) per component, at most
+    four; ``bits`` None is the storage width.  Field widths over 64 bits in
+    all raise NotImplementedError."""
+
+    def __init__(self, comps):
+        comps = [(str(n), str(s), b, bool(nu)) for n, s, b, nu in comps]
+        if not comps:
+            raise ValueError("a composite key needs a component")
+        if len(comps) > MAX_KEYS:
+            raise NotImplementedError(f"GROUP BY {len(comps)} key columns: at most {MAX_KEYS} "
+                                      "components are packed into the 64-bit key")
+        for n, s, b, nu in comps:
+            if s not in KEY_CODE:
+                raise NotImplementedError(f"hash GROUP BY component {n} of storage {s}: integer "
+                                          "columns")
+            full = 8 * np.dtype(s).itemsize
+            if b is not None and not 1 <= int(b) <= full:
+                raise ValueError(f"bits={b} for {n}: 1 <= bits <= {full}, its storage width")
+        widths = [(int(b) if b is not None else 8 * np.dtype(s).itemsize) + int(nu)
+                  for _, s, b, nu in comps]
+        if sum(widths) > 64:
+            each = ", ".join(f"{n}: {w}" + (" (1 for nulls)" if nu else "")
+                             for (n, _, _, nu), w in zip(comps, widths))
+            raise NotImplementedError(
+                f"GROUP BY key of {sum(widths)} bits ({each}): the packed key holds 64; declare "
+                "narrower value ranges with bits={column: n}")
+        out, top = [], sum(widths)
+        for (n, s, b, nu), w in zip(comps, widths):
+            top -= w
+            out.append(KeyComp(n, s, w - int(nu), nu, top))
+        self.comps: List[KeyComp] = out
+
+    def __len__(self) -> int:
+        return len(self.comps)
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, KeySpec) and self.comps == other.comps
+
+    def __repr__(self) -> str:
+        return "KeySpec(" + ", ".join(f"{c.name}:{c.storage}/{c.bits}" + ("?" if c.nullable else "")
+                                      for c in self.comps) + ")"
+
+    @property
+    def names(self) -> List[str]:
+        return [c.name for c in self.comps]
+
+    def args(self):
+        """The strom_group_keys argument."""
+        from .._native import GroupKeys
+        a = GroupKeys()
+        a.nkeys = len(self.comps)
+        for i, c in enumerate(self.comps):
+            a.k[i].type, a.k[i].bits = KEY_CODE[c.storage], c.bits
+            a.k[i].shift, a.k[i].nullable = c.shift, int(c.nullable)
+        return a
+
+    def pack_why(self, columns, valids):
+        """(packed uint64, bad int8): ``bad`` is -1 for a row whose every
+        component fits, else the first component that does not (a value
+        outside its ``bits``, or a null in a component that is not
+        nullable); such a row's packed word means nothing."""
+        n = len(columns[0]) if len(columns) else 0
+        packed = np.zeros(n, np.uint64)
+        bad = np.full(n, -1, np.int8)
+        for i, c in enumerate(self.comps):
+            v = np.asarray(columns[i])[:n]
+            if v.dtype.kind not in "iu":
+                raise NotImplementedError(f"component {c.name} of dtype {v.dtype}: integer columns")
+            if c.signed:
+                u = v.astype(np.int64).view(np.uint64) + np.uint64(1 << (c.bits - 1))
+            else:
+                u = v.astype(np.uint64)
+            fits = np.ones(n, bool) if c.bits == 64 else (u >> np.uint64(c.bits)) == 0
+            ok = valids[i] if valids is not None else None
+            if ok is not None:
+                null = ~np.asarray(ok, bool)[:n]
+                u = np.where(null, np.uint64((1 << c.bits) & (2**64 - 1)), u)
+                fits = np.where(null, c.nullable, fits)
+            bad = np.where((bad < 0) & ~fits, np.int8(i), bad)
+            packed |= np.where(fits, u, np.uint64(0)) << np.uint64(c.shift)
+        return packed, bad
+
+    def pack(self, columns, valids=None):
+        """(packed uint64, fits bool) of rows given per component as values
+        (integer arrays) and validity (bool array or None)."""
+        packed, bad = self.pack_why(columns, valids)
+        return packed, bad < 0
+
+    def unpack(self, packed):
+        """([values per component, in its storage dtype], [valid bool per
+        component]) of packed keys; a null's value is 0."""
+        p = np.asarray(packed, np.uint64)
+        vals, oks = [], []
+        for c in self.comps:
+            f = p >> np.uint64(c.shift)
+            null = np.zeros(len(p), bool)
+            if c.nullable:
+                null = ((f >> np.uint64(c.bits)) & np.uint64(1)).astype(bool)
+            if c.bits < 64:
+                f = f & np.uint64((1 << c.bits) - 1)
+            if c.signed:
+                f = (f - np.uint64(1 << (c.bits - 1))).view(np.int64)
+            v = f.astype(np.dtype(c.storage))
+            v[null] = 0
+            vals.append(v)
+            oks.append(~null)
+        return vals, oks
+
+
 # ------------------------------------------------------------ numpy twin
 @dataclass
 class Groups:
     """key -> accumulators: ``keys`` ascending by value, ``block`` a colagg
-    block of ``GroupLayout(entries, len(keys) + 1)`` (last slot: null keys)."""
+    block of ``GroupLayout(entries, len(keys) + 1)`` (last slot: null keys).
+    With a composite key ``keys`` are the packed words (uint64) and ``spec``
+    the KeySpec that packed them; the null keys' slot stays empty."""
     entries: List[A.Entry]
     keys: np.ndarray
     block: np.ndarray
+    spec: Optional[KeySpec] = None
 
     @property
     def layout(self) -> GroupLayout:
@@ -103,10 +256,11 @@ class Groups:
         return A.entry_arrays(self.layout, self.block, e)
 
 
-def empty_groups(entries: Sequence[A.Entry], unsigned: bool = False) -> Groups:
+def empty_groups(entries: Sequence[A.Entry], unsigned: bool = False,
+                 spec: Optional[KeySpec] = None) -> Groups:
     ents = list(entries)
-    return Groups(ents, np.zeros(0, np.uint64 if unsigned else np.int64),
-                  A.new_block(GroupLayout(ents, 1)))
+    return Groups(ents, np.zeros(0, np.uint64 if unsigned or spec is not None else np.int64),
+                  A.new_block(GroupLayout(ents, 1)), spec)
 
 
 def host_group_agg(entries: Sequence[A.Entry], sel, key_values, key_valid, cols) -> Groups:
@@ -129,6 +283,21 @@ def host_group_agg(entries: Sequence[A.Entry], sel, key_values, key_valid, cols)
     return Groups(ents, keys, block)
 
 
+def host_group_agg_multi(entries: Sequence[A.Entry], sel, spec: KeySpec, columns, valids, cols):
+    """One batch through the composite-key twin: ``columns`` / ``valids`` the
+    components (values, validity or None), packed by ``spec`` as the kernel
+    packs them.  Returns (Groups with the packed keys ascending, the selected
+    rows per component that did not fit it and were left out)."""
+    sel = np.asarray(sel, bool)
+    n = len(sel)
+    packed, bad = spec.pack_why([np.asarray(c)[:n] for c in columns],
+                                [None if v is None else np.asarray(v, bool)[:n] for v in valids])
+    misfit = np.bincount(bad[sel & (bad >= 0)].astype(np.int64), minlength=len(spec))
+    g = host_group_agg(entries, sel & (bad < 0), packed, None, cols)
+    g.spec = spec
+    return g, misfit.astype(np.int64)
+
+
 def _spread(g: Groups, keys: np.ndarray) -> np.ndarray:
     """``g``'s block over the key set ``keys`` (a superset of its own)."""
     lay = GroupLayout(g.entries, len(keys) + 1)
@@ -149,19 +318,23 @@ def merge(a: Groups, b: Groups) -> Groups:
     if [(e.ops, e.dtype) for e in a.entries] != [(e.ops, e.dtype) for e in b.entries] or \
             a.keys.dtype != b.keys.dtype:
         raise ValueError("merge: different entries or key types")
+    if a.spec != b.spec:
+        raise ValueError(f"merge: keys packed differently ({a.spec} and {b.spec})")
     keys = np.union1d(a.keys, b.keys)
     lay = GroupLayout(a.entries, len(keys) + 1)
-    return Groups(a.entries, keys, A.merge_blocks(lay, _spread(a, keys), _spread(b, keys)))
+    return Groups(a.entries, keys, A.merge_blocks(lay, _spread(a, keys), _spread(b, keys)),
+                  a.spec)
 
 
 # ------------------------------------------------------------ device
 class DeviceGroups:
     """A table on the device: ``table`` int64[HDR_WORDS + capacity] (header,
     key words), ``acc`` int64[narrays, capacity + 2] — entry e's arrays are
-    rows ``row[e] .. row[e] + popcount(ops)``."""
+    rows ``row[e] .. row[e] + popcount(ops)``.  ``spec``: the table holds
+    composite keys packed by that KeySpec (uint64 words)."""
 
     def __init__(self, entries: Sequence[A.Entry], groups: int, device, unsigned: bool = False,
-                 stream=None):
+                 stream=None, spec: Optional[KeySpec] = None):
         import torch
         from ._util import check, lib, ptr, stream_handle
         self.entries = list(entries)
@@ -170,7 +343,8 @@ class DeviceGroups:
                 raise ValueError("an entry needs COUNT, SUM, MIN or MAX")
         self.groups = check_groups(groups)
         self.capacity = capacity(self.groups)
-        self.unsigned = bool(unsigned)
+        self.spec = spec
+        self.unsigned = bool(unsigned) or spec is not None
         self.stride = self.capacity + 2
         self.row = np.concatenate([[0], np.cumsum([A.nacc(e.ops) for e in self.entries])])
         nbytes = 8 * (HDR_WORDS + self.capacity + int(self.row[-1]) * self.stride)
@@ -222,6 +396,32 @@ def group_codes(t: DeviceGroups, key_code: int, keys, nwords: int, src, dst, cod
     check(lib().strom_group_codes(key_code, ptr(t.table), t.capacity, ptr(keys), keys.shape[0],
                                   nwords, ptr(src), ptr(dst), ptr(codes), stream_handle(stream)),
           "group_codes")
+
+
+def group_codes_multi(t: DeviceGroups, keys, nwords: int, src, dst, codes, stream=None) -> None:
+    """strom_group_codes_multi over a group with the table's KeySpec:
+    ``keys`` the components' strom_filter_batch tables, int64
+    (len(spec), nbatches, 5), all over the same batches; the rest as
+    group_codes.  A component's values may be the code buffers themselves."""
+    import torch
+    from ._util import check, lib, ptr, require_cuda, stream_handle
+    from .colfilter import BATCH_FIELDS
+    if t.spec is None:
+        raise ValueError("group_codes_multi: the table was made without a KeySpec")
+    for x, name in ((keys, "keys"), (src, "src"), (dst, "dst"), (codes, "codes")):
+        require_cuda(x, name)
+    if keys.dtype != torch.int64 or keys.dim() != 3 or keys.shape[0] != len(t.spec) or \
+            keys.shape[2] != BATCH_FIELDS or not keys.is_contiguous():
+        raise ValueError(f"keys: contiguous int64 ({len(t.spec)}, n, 5)")
+    if codes.shape != keys.shape[1:] or codes.dtype != torch.int64:
+        raise ValueError("codes: a table of the same batches")
+    if src.numel() < nwords or dst.numel() < nwords:
+        raise ValueError("bitmap too small")
+    if not nwords or not keys.shape[1]:
+        return
+    check(lib().strom_group_codes_multi(t.spec.args(), ptr(t.table), t.capacity, ptr(keys),
+                                        keys.shape[1], nwords, ptr(src), ptr(dst), ptr(codes),
+                                        stream_handle(stream)), "group_codes_multi")
 
 
 def group_agg(t: DeviceGroups, e: int, bitmap, nwords: int, vals, codes, combine=None,
@@ -295,4 +495,4 @@ def compact(t: DeviceGroups):
         n = A.nacc(t.entries[e].ops)
         block[lay.off[e]:lay.off[e] + n * lay.nslots] = \
             rows[int(t.row[e]):int(t.row[e]) + n][:, cols].reshape(-1)
-    return hdr, Groups(t.entries, keys.astype(wide, copy=False), block)
+    return hdr, Groups(t.entries, keys.astype(wide, copy=False), block, t.spec)

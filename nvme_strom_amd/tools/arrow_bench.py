@@ -471,6 +471,95 @@ def hashagg_row(path: str, fd: int, a, col) -> dict:
     return row
 
 
+def make_pairs_file(path: str, rows: int, batch_rows: int, side: int = 1024, seed: int = 9,
+                    codec: str = "lz4") -> None:
+    """``id`` int64 (the row number), ``a`` and ``b`` int32 uniform over
+    ``side`` values each, and ``k`` int64 = a * 2^32 + b: the same pairs as
+    one column."""
+    import pyarrow as pa
+    import pyarrow.ipc as ipc
+    if os.path.exists(path):
+        return
+    schema = pa.schema([("id", pa.int64()), ("a", pa.int32()), ("b", pa.int32()),
+                        ("k", pa.int64())])
+    rng = np.random.default_rng(seed)
+    tmp = path + ".tmp"
+    with ipc.new_file(tmp, schema, options=ipc.IpcWriteOptions(compression=codec)) as w:
+        for b0 in range(0, rows, batch_rows):
+            n = min(batch_rows, rows - b0)
+            av = rng.integers(0, side, n).astype(np.int32)
+            bv = rng.integers(0, side, n).astype(np.int32)
+            w.write_batch(pa.record_batch(
+                [pa.array(np.arange(b0, b0 + n, dtype=np.int64)), pa.array(av), pa.array(bv),
+                 pa.array(av.astype(np.int64) * (1 << 32) + bv)], schema=schema))
+    os.replace(tmp, path)
+
+
+def hashagg2_row(path: str, a) -> dict:
+    """``aggregate([], [count(*), sum(id)], by=HashBy(["a", "b"], groups=1 <<
+    20))`` — two int32 key columns, a million distinct pairs — alternated
+    with ``by=HashBy("k")``, the same pairs packed in one int64 column of the
+    same file (8 key bytes a row either way).  The file is evicted before
+    every run; the two-key result is verified against numpy."""
+    import torch
+
+    import nvme_strom_amd as S
+    from nvme_strom_amd.models.arrow_scan import ArrowScan, HashBy
+    aggs = [("count", None), ("sum", "id")]
+    fd = os.open(path, os.O_RDONLY)
+    sc = ArrowScan(path, "cuda", slot_bytes=a.slot_mib << 20, nslots=a.nslots or None,
+                   chunk_sz=(a.chunk_kib << 10) or None)
+
+    def timed(fn):
+        S.evict_file(fd)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t, out
+    two_s, one_s = [], []
+    two_sync, one_sync = [], []       # up to the scan's sync: without the result's Python keys
+    try:
+        by2, by1 = HashBy(["a", "b"], groups=1 << 20), HashBy("k", groups=1 << 20)
+        timed(lambda: sc.aggregate([], aggs, by=by2))             # cold: plans, slots, code
+        timed(lambda: sc.aggregate([], aggs, by=by1))
+        for k in range(max(1, a.agg_pairs)):
+            for what in (("two", "one") if k % 2 == 0 else ("one", "two")):
+                if what == "two":
+                    dt, out = timed(lambda: sc.aggregate([], aggs, by=by2))
+                    two_s.append(dt)
+                    two_sync.append(out.seconds["total_s"])
+                else:
+                    dt, one = timed(lambda: sc.aggregate([], aggs, by=by1))
+                    one_s.append(dt)
+                    one_sync.append(one.seconds["total_s"])
+            _log(f"hashagg2 pair {k}: HashBy([a, b]) {two_s[-1] * 1e3:.1f} ms, HashBy(k) "
+                 f"{one_s[-1] * 1e3:.1f} ms")
+    finally:
+        sc.close()
+        os.close(fd)
+    kv = column_np(path, "k")[0]
+    keys, inv = np.unique(kv, return_inverse=True)
+    want_sum = np.zeros(len(keys), np.int64)
+    np.add.at(want_sum, inv, column_np(path, "id")[0])
+    ok = bool(out.keys == list(zip((keys >> 32).tolist(), (keys & 0xFFFFFFFF).tolist())) and
+              np.array_equal(out.count_all, np.bincount(inv, minlength=len(keys))) and
+              np.array_equal(out.get("sum", "id")[0], want_sum) and
+              one.keys == keys.tolist() and np.array_equal(one.count_all, out.count_all))
+    ratios = [x / y for x, y in zip(two_s, one_s)]
+    row = dict(aggs=[list(x) for x in aggs], by="HashBy([a, b])", against="HashBy(k)",
+               groups_param=1 << 20, distinct_keys=len(keys), selected=out.selected, verified=ok,
+               bytes_read=out.bytes_read, column_bytes=out.column_bytes, groups=out.groups,
+               two_keys_ms=[round(x * 1e3, 2) for x in two_s],
+               one_key_ms=[round(x * 1e3, 2) for x in one_s],
+               median_ratio_two_over_one=round(float(np.median(ratios)), 4),
+               two_keys_to_sync_ms=[round(x * 1e3, 2) for x in two_sync],
+               one_key_to_sync_ms=[round(x * 1e3, 2) for x in one_sync],
+               median_ratio_to_sync=round(float(np.median(two_sync) / np.median(one_sync)), 4),
+               two_keys_breakdown_s={k: round(v, 4) for k, v in out.seconds.items()})
+    _log(json.dumps(row))
+    return row
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1 << 27)
@@ -500,7 +589,9 @@ def main(argv=None) -> int:
     ap.add_argument("--join-pairs", type=int, default=15)
     ap.add_argument("--hashagg", action="store_true",
                     help="add the row GROUP BY HashBy(val), a million distinct keys, alternated "
-                         "with the same aggregates without a key (--agg-pairs pairs)")
+                         "with the same aggregates without a key (--agg-pairs pairs), and "
+                         "the row GROUP BY HashBy([a, b]), a million pairs of two int32 "
+                         "columns, alternated with HashBy of the pairs as one int64 column")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     import torch
@@ -615,6 +706,12 @@ def main(argv=None) -> int:
             res["hashagg"] = hashagg_row(path, fd, a, col)
     finally:
         os.close(fd)
+    if a.hashagg:
+        # GROUP BY two key columns, on a file of its own (the main one has no
+        # two integer columns of few values)
+        ppath = os.path.join(a.dir, f"pairs_{a.rows}_{a.batch_rows}{tag}.arrow")
+        make_pairs_file(ppath, a.rows, a.batch_rows, codec=a.codec)
+        res["hashagg2"] = hashagg2_row(ppath, a)
     if a.strings:
         import datetime as _dt
 
@@ -661,7 +758,8 @@ def main(argv=None) -> int:
     res["verified"] = all(c["verified"] for c in res["columns"].values()) and \
         all(r["verified"] for r in res.get("agg", {}).values()) and \
         all(r["verified"] for r in res.get("join", {}).values()) and \
-        res.get("hashagg", {}).get("verified", True)
+        res.get("hashagg", {}).get("verified", True) and \
+        res.get("hashagg2", {}).get("verified", True)
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:

@@ -288,7 +288,9 @@ def _hashagg_rows(n, dev, log, column_filter):
     warm-up inserted them).  ``_c0`` / ``_c1``: the accumulate launch alone
     without / with the in-word combining of the first row's code.  Keys:
     uniform over 256, 64 Ki, 1 Mi and 8 Mi values, a sorted column of 64 Ki
-    values, and one with every other row on one key."""
+    values, and one with every other row on one key.  ``hashagg_codes2_*``:
+    the composite-key find-or-insert on two int32 columns next to the
+    single-key one on the same pairs as one int64 column."""
     from nvme_strom_amd.ops import colagg as A
     from nvme_strom_amd.ops import colgroup as G
     nv = n // 8
@@ -351,6 +353,43 @@ def _hashagg_rows(n, dev, log, column_filter):
         print(f"hashagg {name}: capacity {int(hdr[G.H_CAPACITY])}, {int(hdr[G.H_NKEYS])} keys, "
               f"{int(hdr[G.H_OVERFLOW])} overflowed rows", file=sys.stderr, flush=True)
         del k, tk, t
+    # composite keys: strom_group_codes_multi on two int32 columns next to
+    # strom_group_codes on one int64 column that holds the same pairs packed
+    # (a * 2^32 + b: the same distinct count, 8 key bytes a row on both
+    # sides), uniform over 64 Ki and 1 Mi pairs and sorted; the two launches
+    # alternate, three rounds, and each row is its fastest round
+    spec = G.KeySpec([("a", "i4", None, False), ("b", "i4", None, False)])
+    for tag, side in (("uniform65536", 256), ("uniform1048576", 1024), ("sorted64Ki", 256)):
+        a = torch.randint(0, side, (nv,), dtype=torch.int64, device=dev)
+        b = torch.randint(0, side, (nv,), dtype=torch.int64, device=dev)
+        k = a * (1 << 32) + b
+        if tag.startswith("sorted"):
+            k = torch.sort(k)[0]
+            a, b = k >> 32, k & 0xFFFFFFFF
+        a32, b32 = a.to(torch.int32), b.to(torch.int32)
+        del a, b
+        tk = tab(k)
+        tab2 = torch.stack([tab(a32), tab(b32)]).contiguous()
+        t1 = G.DeviceGroups(ents[:1], side * side, dev)
+        t2 = G.DeviceGroups(ents[:1], side * side, dev, spec=spec)
+
+        def single():
+            G.group_codes(t1, G.KEY_CODE["i8"], tk, nwords, ones, dst, ctab)
+
+        def multi():
+            G.group_codes_multi(t2, tab2, nwords, ones, dst, ctab)
+        best = {"single": [], "multi": []}
+        for _ in range(3):
+            best["single"].append(timed(single, 3))
+            best["multi"].append(timed(multi, 3))
+        s1, s2 = min(best["single"]), min(best["multi"])
+        log(f"hashagg_codes2_{tag}_single_i64", s1, nv * 8)
+        log(f"hashagg_codes2_{tag}", s2, nv * 8)
+        h1, h2 = t1.header(), t2.header()
+        print(f"hashagg_codes2 {tag}: multi / single = {s2 / s1:.3f}; {int(h1[G.H_NKEYS])} and "
+              f"{int(h2[G.H_NKEYS])} keys, {int(h2[G.H_OVERFLOW])} overflowed, "
+              f"{int(h2[G.H_RANGE:].sum())} out of range", file=sys.stderr, flush=True)
+        del k, tk, tab2, a32, b32, t1, t2
 
 
 def _mvcc_rows(n, dev, log):

@@ -29,6 +29,7 @@ kmod/nvme_strom.c:1488-1604) is what fetches the scattered buffers.
 """
 from __future__ import annotations
 
+import gc
 import os
 import struct
 import time
@@ -330,6 +331,35 @@ class _HashRun:
 
 
 @dataclass
+class _Run:
+    """One scan as _compute's stages see it: its totals over the groups and
+    where its results go.  A stage whose field is None is not called."""
+    count: torch.Tensor           # selected rows so far (device)
+    err: torch.Tensor             # failed decodes so far (device)
+    wait_s: float = 0.0
+    bytes_read: int = 0
+    column_bytes: int = 0
+    marks: list = field(default_factory=list)    # (group, event, clock)
+    join: Optional[_JoinRun] = None
+    hash: Optional[_HashRun] = None
+    # rows (scan_where): the row ids and the projection behind their cursors
+    out: Optional[torch.Tensor] = None
+    cursor: Optional[torch.Tensor] = None
+    ccursor: Optional[torch.Tensor] = None       # characters written
+    pout: Optional[torch.Tensor] = None
+    pvalid: Optional[torch.Tensor] = None
+    pchars: Optional[torch.Tensor] = None
+    poff: Optional[torch.Tensor] = None
+    owidth: int = 4                              # offset bytes of a projected utf8/binary column
+    pattr: bool = False                          # project the joined attribute's codes
+    pcol: Optional[int] = None                   # plan column of the projection
+    # aggregate
+    agg: Optional[_AggSpec] = None
+    block: Optional[torch.Tensor] = None         # the scan's accumulator block
+    block_ready: Optional[torch.cuda.Event] = None   # ... initialised (emit stream)
+
+
+@dataclass
 class _Buf:
     off: int          # file offset of the stored buffer
     length: int       # stored bytes (prefix + frame when compressed)
@@ -427,6 +457,44 @@ class _Slot:
     pin: Optional[torch.Tensor] = None     # pinned arena for the group's tables
     keybuf: Optional[torch.Tensor] = None  # int32 per row: the joined attribute's code
     pin_off: int = 0
+
+
+class _Tables:
+    """One batch table per referenced column of a group in its slot: resolved
+    on the host when first asked for, uploaded once per group."""
+
+    def __init__(self, upload, s: _Slot, g: _Group, base: int, dec_base: int):
+        self.upload, self.s, self.g, self.base, self.dec_base = upload, s, g, base, dec_base
+        self.tabs: Dict[int, torch.Tensor] = {}
+        self.tabs_np: Dict[int, np.ndarray] = {}
+
+    def _host(self, col: int) -> np.ndarray:
+        """The group's strom_qual_batch table for one column: values,
+        validity and character pointers resolved against this slot."""
+        if col not in self.tabs_np:
+            g = self.g
+            t = self.tabs_np[col] = g.table.copy()
+            kind, rel = g.ptr_kind[:, col, :], g.ptr_rel[:, col, :]
+            ptrs = np.where(kind == 1, self.base + rel,
+                            np.where(kind == 2, self.dec_base + rel, 0))
+            t[:, 0], t[:, 1], t[:, 5] = ptrs[:, 0], ptrs[:, 1], ptrs[:, 2]
+            t[:, 6] = g.aux_len[:, col]
+        return self.tabs_np[col]
+
+    def host5(self, col: int) -> np.ndarray:
+        """The strom_filter_batch prefix of the column's table, on the host."""
+        return self._host(col)[:, :BATCH_FIELDS]
+
+    def qual(self, col: int) -> torch.Tensor:
+        """The column's full table on the device."""
+        if col not in self.tabs:
+            self.tabs[col] = self.upload(self.s, self._host(col))
+            self.s.keep.append(self.tabs[col])
+        return self.tabs[col]
+
+    def dev5(self, col: int) -> torch.Tensor:
+        """The strom_filter_batch prefix of ``qual(col)``, on the device."""
+        return self.qual(col)[:, :BATCH_FIELDS].contiguous()
 
 
 def _up64(n: int) -> int:
@@ -883,17 +951,6 @@ class ArrowScan:
         res, landed = self.reader.submit(self._hbm, s.off, g.ids.astype(np.uint32), wb=wb)
         s.pending = (res, landed, g)
 
-    @staticmethod
-    def _pointers(g: _Group, col: int, base: int, dec_base: int) -> np.ndarray:
-        """The group's strom_qual_batch table for one column: values,
-        validity and character pointers resolved against this slot."""
-        t = g.table.copy()
-        kind, rel = g.ptr_kind[:, col, :], g.ptr_rel[:, col, :]
-        ptrs = np.where(kind == 1, base + rel, np.where(kind == 2, dec_base + rel, 0))
-        t[:, 0], t[:, 1], t[:, 5] = ptrs[:, 0], ptrs[:, 1], ptrs[:, 2]
-        t[:, 6] = g.aux_len[:, col]
-        return t
-
     def _upload(self, s: "_Slot", arr: np.ndarray) -> torch.Tensor:
         """``arr`` as a device tensor, copied on the current stream through
         the slot's pinned arena.  A pinned allocation per group (pin_memory())
@@ -918,254 +975,241 @@ class ArrowScan:
         d.copy_(host, non_blocking=True)
         return d.view(torch.from_numpy(a[:0].reshape(-1)).dtype).reshape(a.shape)
 
-    def _compute(self, k: int, spec, proj, state) -> None:
+    def _compute(self, k: int, spec, run: _Run) -> None:
+        """Group k in its slot: every stage but the emit on the slot's stream."""
         s = self._slots[k % len(self._slots)]
+        g, region = self._land(k, s, run)
+        with torch.cuda.stream(s.stream):
+            self._decode(k, s, g, region, run)
+            t = _Tables(self._upload, s, g, region.data_ptr(), s.dec.data_ptr())
+            bitmap = self._filter(s, g, t, spec, counts=run.join is None)
+            # the table of the slot's key buffer once a stage writes codes there
+            d_codes = None
+            if run.join is not None:
+                bitmap, d_codes = self._probe(s, g, t, run.join, bitmap)
+            if run.hash is not None:
+                bitmap, d_codes = self._group_codes(s, g, t, run.hash, bitmap)
+            run.marks.append((k, "quals_queued", time.perf_counter()))
+            # emit tables: the strom_filter_batch prefix of the qual tables
+            any_col = spec[0][0][0] if spec else (run.join.col if run.join is not None else 0)
+            d_rows = t.dev5(any_col)
+            args = d_proj = None
+            if run.agg is not None:
+                args = self._accumulate(s, g, t, run, any_col, bitmap,
+                                        d_codes.data_ptr() if d_codes is not None else 0)
+            if run.pattr:
+                d_proj = d_codes                 # the joined attribute's codes
+            elif run.pcol is not None:
+                d_proj = t.qual(run.pcol) if run.pchars is not None else t.dev5(run.pcol)
+            s.keep += [d_rows] + ([d_proj] if d_proj is not None else [])
+        self._emit(s, g, run, d_rows, d_proj, args)
+        run.bytes_read += g.read_bytes
+        run.column_bytes += g.column_bytes
+        run.marks.append((k, "launched", time.perf_counter()))
+
+    def _land(self, k: int, s: _Slot, run: _Run) -> Tuple[_Group, torch.Tensor]:
+        """The slot's read finished: (its group, the group's bytes in file order)."""
         res, landed, g = s.pending
         s.pending = None
         s.pin_off = 0
         t0 = time.perf_counter()
         self.reader.finish(res)
         t1 = time.perf_counter()
-        state["wait_s"] += t1 - t0
-        state["marks"].append((k, "landed", t1))
+        run.wait_s += t1 - t0
+        run.marks.append((k, "landed", t1))
         region = self._hbm.tensor[s.off:s.off + g.span]
         nr_ram = getattr(res, "nr_ram", 0)            # extent reads: all from storage
         # write-back copies of page-cache chunks (FileReader.submit without a
         # BAR) were queued on the current stream; only then wait for it (a
         # wait on the default stream also waits for whatever blocking
         # streams hold)
-        cs = s.stream
         if nr_ram:
-            cs.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(cs):
-            if nr_ram and not np.array_equal(landed, g.ids.astype(np.uint32)):
-                # page-cache chunks landed at the tail: restore chunk order
+            s.stream.wait_stream(torch.cuda.current_stream(self.device))
+        if nr_ram and not np.array_equal(landed, g.ids.astype(np.uint32)):
+            # page-cache chunks landed at the tail: restore chunk order
+            with torch.cuda.stream(s.stream):
                 if s.scratch is None:
                     s.scratch = torch.empty(s.cap, dtype=torch.uint8, device=self.device)
                 tmp = s.scratch[:region.numel()]
                 tmp.copy_(region)
                 chunk_scatter(tmp, region, landing_positions(g.ids.astype(np.uint32), landed,
                                                              res.nr_ssd), self.chunk_sz)
-            base = region.data_ptr()
-            dec_base = s.dec.data_ptr()
-            descs = g.descs if g.descs is not None else g.descs_lanes
-            for dsc, need, lanes in ((g.descs, g.need, False), (g.descs_lanes, g.need_lanes, True)):
-                if dsc is None:
-                    continue
-                # every compressed buffer of every scanned column: one launch
-                # (two when some are literal-heavy LZ4)
-                d_desc = self._upload(s, dsc.view(np.uint8))
-                d_need = self._upload(s, need)
-                status = torch.empty(len(dsc), dtype=torch.int32, device=self.device)
-                D.decompress_async(self._codec, region, s.dec, d_desc, status, stream=cs,
-                                   lanes=lanes, zstd_mode=self.ZSTD_MODE)
-                # status = decoded bytes; short or failed -> error count
-                s.err += ((status < d_need) | (status < 0)).sum()
-                s.keep += [d_desc, d_need, status]
-                state["marks"].append((k, "decode_queued", time.perf_counter()))
-            # one batch table per referenced column, uploaded once per group
-            tabs: Dict[int, torch.Tensor] = {}
+        return g, region
 
-            tabs_np: Dict[int, np.ndarray] = {}
+    def _decode(self, k: int, s: _Slot, g: _Group, region: torch.Tensor, run: _Run) -> None:
+        for dsc, need, lanes in ((g.descs, g.need, False), (g.descs_lanes, g.need_lanes, True)):
+            if dsc is None:
+                continue
+            # every compressed buffer of every scanned column: one launch
+            # (two when some are literal-heavy LZ4)
+            d_desc = self._upload(s, dsc.view(np.uint8))
+            d_need = self._upload(s, need)
+            status = torch.empty(len(dsc), dtype=torch.int32, device=self.device)
+            D.decompress_async(self._codec, region, s.dec, d_desc, status, stream=s.stream,
+                               lanes=lanes, zstd_mode=self.ZSTD_MODE)
+            # status = decoded bytes; short or failed -> error count
+            s.err += ((status < d_need) | (status < 0)).sum()
+            s.keep += [d_desc, d_need, status]
+            run.marks.append((k, "decode_queued", time.perf_counter()))
 
-            def table(col: int) -> torch.Tensor:
-                if col not in tabs:
-                    t = tabs_np[col] = self._pointers(g, col, base, dec_base)
-                    tabs[col] = self._upload(s, t)
-                    s.keep.append(tabs[col])
-                return tabs[col]
-            jn = state.get("join")
-            # the CNF qualifier list: clause 0 writes the bitmap (its
-            # predicates ORed in place), a later single-predicate clause ANDs
-            # into it, a later OR-clause collects in the scratch bitmap and
-            # its last predicate ORs that in and ANDs into the bitmap; the
-            # last launch's count is the selection's
-            for ci, clause in enumerate(spec):
-                for j, (col, cq) in enumerate(clause):
-                    last = jn is None and ci == len(spec) - 1 and j == len(clause) - 1
-                    cnt = s.count if last else s.junk
-                    if ci == 0:
-                        qual_batched(cq, table(col), g.words, s.bitmap, cnt, stream=cs,
-                                     or_src=s.bitmap if j else None)
-                    elif len(clause) == 1:
-                        qual_batched(cq, table(col), g.words, s.bitmap, cnt, stream=cs,
-                                     and_dst=True)
-                    elif j < len(clause) - 1:
-                        qual_batched(cq, table(col), g.words, s.bm2, cnt, stream=cs,
-                                     or_src=s.bm2 if j else None)
-                    else:
-                        qual_batched(cq, table(col), g.words, s.bitmap, cnt, stream=cs,
-                                     or_src=s.bm2, and_dst=True)
-            bitmap = s.bitmap
-            if not spec:
-                # no qualifier (aggregate only): every row of every batch,
-                # each batch's last word bounded by its rows
-                if g.ones is None:
-                    g.ones = _all_rows_bitmap(g.table[:, 2])
-                bitmap = self._upload(s, g.ones)
-                s.keep.append(bitmap)
-            d_kout = None
-            kout_ptr = 0
-            if jn is not None:
-                # the probe, the list's last launch (and_dst semantics, its
-                # count is the selection's): the fk's batch table and, when an
-                # attribute is wanted, the table of the slot's key buffer —
-                # batch b's codes at row word_base * 64 — go up in one copy
-                n = len(g.table)
-                fk5 = (tabs_np[jn.col] if jn.col in tabs_np else
-                       self._pointers(g, jn.col, base, dec_base))[:, :BATCH_FIELDS]
-                both = [fk5]
-                if jn.attr is not None:
-                    if s.keybuf is None or s.keybuf.numel() < s.bitmap.numel() * 64:
-                        s.keybuf = torch.empty(s.bitmap.numel() * 64, dtype=torch.int32,
-                                               device=self.device)
-                    k5 = fk5.copy()
-                    k5[:, 0] = s.keybuf.data_ptr() + g.table[:, 3] * 256
-                    k5[:, 1] = 0
-                    both.append(k5)
-                d_j = self._upload(s, np.stack(both))
-                s.keep.append(d_j)
-                if jn.attr is not None:
-                    d_kout = d_j[1]
-                    kout_ptr = d_kout.data_ptr()
-                J.probe(jn.dev, jn.code, d_j[0], g.words, bitmap, s.bitmap, s.count,
-                        how=J.HOW[jn.how], key_out=d_kout, stream=cs)
-                bitmap = s.bitmap
-            hs = state.get("hash")
-            if hs is not None:
-                # by=HashBy: find-or-insert of the key column over the bitmap
-                # the qualifiers and the probe left; each row's code goes into
-                # the slot's key buffer, the accumulate launches' key column
-                if s.keybuf is None or s.keybuf.numel() < s.bitmap.numel() * 64:
-                    s.keybuf = torch.empty(s.bitmap.numel() * 64, dtype=torch.int32,
-                                           device=self.device)
-                c5 = g.table[:, :BATCH_FIELDS].copy()
-                c5[:, 0] = s.keybuf.data_ptr() + g.table[:, 3] * 256
-                c5[:, 1] = 0
-                if hs.cols is not None:
-                    # a composite key: every component's table, the join
-                    # attribute's being the code buffers' own (the launch runs
-                    # in place there: a lane reads its row's components before
-                    # it stores the row's code), then the code buffers'
-                    k5 = [c5 if c is None else
-                          (tabs_np[c] if c in tabs_np else
-                           self._pointers(g, c, base, dec_base))[:, :BATCH_FIELDS]
-                          for c in hs.cols]
-                    d_h = self._upload(s, np.stack(k5 + [c5]))
-                    s.keep.append(d_h)
-                    G.group_codes_multi(hs.dev, d_h[:-1], g.words, bitmap, s.bitmap, d_h[-1],
-                                        stream=cs)
+    def _filter(self, s: _Slot, g: _Group, t: _Tables, spec, counts: bool) -> torch.Tensor:
+        """The CNF qualifier list: clause 0 writes the bitmap (its predicates
+        ORed in place), a later single-predicate clause ANDs into it, a later
+        OR-clause collects in the scratch bitmap and its last predicate ORs
+        that in and ANDs into the bitmap.  ``counts``: the list's last launch
+        counts the selection (no later stage does).  Returns the bitmap of
+        the selection."""
+        for ci, clause in enumerate(spec):
+            for j, (col, cq) in enumerate(clause):
+                last = counts and ci == len(spec) - 1 and j == len(clause) - 1
+                cnt = s.count if last else s.junk
+                if ci == 0:
+                    dst, how = s.bitmap, dict(or_src=s.bitmap if j else None)
+                elif len(clause) == 1:
+                    dst, how = s.bitmap, dict(and_dst=True)
+                elif j < len(clause) - 1:
+                    dst, how = s.bm2, dict(or_src=s.bm2 if j else None)
                 else:
-                    key5 = (tabs_np[hs.col] if hs.col in tabs_np else
-                            self._pointers(g, hs.col, base, dec_base))[:, :BATCH_FIELDS]
-                    d_h = self._upload(s, np.stack([key5, c5]))
-                    s.keep.append(d_h)
-                    G.group_codes(hs.dev, hs.code, d_h[0], g.words, bitmap, s.bitmap, d_h[1],
-                                  stream=cs)
-                bitmap = s.bitmap
-                kout_ptr = d_h[-1].data_ptr()
-            state["marks"].append((k, "quals_queued", time.perf_counter()))
-            # emit tables: the strom_filter_batch prefix of the qual tables
-            any_col = spec[0][0][0] if spec else (jn.col if jn is not None else 0)
-            d_rows = table(any_col)[:, :BATCH_FIELDS].contiguous()
-            agg = state.get("agg")
-            if agg is not None and hs is not None:
-                # the accumulate launches add into the table's arrays in HBM:
-                # no slabs, nothing left for the emit stream to fold
-                n = len(g.table)
-                cols = sorted({any_col if c is None else c for c in agg.entry_cols})
-                t5 = np.stack([(tabs_np[c] if c in tabs_np else
-                                self._pointers(g, c, base, dec_base))[:, :BATCH_FIELDS]
-                               for c in cols])
-                d_t5 = self._upload(s, t5)
-                s.keep.append(d_t5)
-                for e, c in enumerate(agg.entry_cols):
-                    hs.dev.args[e].vals = d_t5.data_ptr() + \
-                        cols.index(any_col if c is None else c) * n * BATCH_FIELDS * 8
-                G.group_agg_many(hs.dev, bitmap, g.words, kout_ptr, n, stream=cs)
-            elif agg is not None:
-                # one aggregate launch per aggregated column on the slot's
-                # stream, each leaving its workgroups' slabs.  The host's time
-                # here delays the next group's read: the columns' batch
-                # tables go up in one copy, the slabs are one allocation and
-                # the launches one native call
-                lay = agg.layout
-                n = len(g.table)
-                cols = sorted({any_col if c is None else c for c in agg.entry_cols} |
-                              ({agg.key_col} if agg.key_col is not None else set()))
-                t5 = np.stack([(tabs_np[c] if c in tabs_np else
-                                self._pointers(g, c, base, dec_base))[:, :BATCH_FIELDS]
-                               for c in cols])
-                d_t5 = self._upload(s, t5)
-                at = {c: d_t5.data_ptr() + i * n * BATCH_FIELDS * 8 for i, c in enumerate(cols)}
-                if g.words not in agg.slab_words:
-                    agg.slab_words[g.words] = [A.slab_words(lay, e, g.words)
-                                               for e in range(len(lay.entries))]
-                sw = agg.slab_words[g.words]
-                d_slabs = torch.empty(sum(sw), dtype=torch.int64, device=self.device)
-                s.keep += [d_t5, d_slabs]
-                args = A.entry_args(lay, state["block"])
-                o = d_slabs.data_ptr()
-                for e, c in enumerate(agg.entry_cols):
-                    args[e].vals = at[any_col if c is None else c]
-                    args[e].slabs = o
-                    o += 8 * sw[e]
-                A.agg_many(lay, args, state["block"], bitmap, g.words,
-                           at[agg.key_col] if agg.key_col is not None else kout_ptr, n, stream=cs)
-            pstr = state.get("pchars") is not None
-            d_proj = None
-            if state.get("pattr"):
-                d_proj = d_kout                  # the joined attribute's codes
-            elif proj is not None:
-                d_proj = table(proj) if pstr else table(proj)[:, :BATCH_FIELDS].contiguous()
-            s.keep += [d_rows] + ([d_proj] if d_proj is not None else [])
-        # decode + filter of successive groups overlap on their slots'
-        # streams; the row-id emit (+ projection gather) runs in group order
-        # on one stream (the output cursor is shared), and frees the slot
+                    dst, how = s.bitmap, dict(or_src=s.bm2, and_dst=True)
+                qual_batched(cq, t.qual(col), g.words, dst, cnt, stream=s.stream, **how)
+        if spec:
+            return s.bitmap
+        # no qualifier (aggregate only): every row of every batch,
+        # each batch's last word bounded by its rows
+        if g.ones is None:
+            g.ones = _all_rows_bitmap(g.table[:, 2])
+        bitmap = self._upload(s, g.ones)
+        s.keep.append(bitmap)
+        return bitmap
+
+    def _code_table(self, s: _Slot, g: _Group) -> np.ndarray:
+        """The batch table of the slot's key buffer (int32 per row of the
+        bitmap, allocated on first use): batch b's codes at row word_base * 64."""
+        if s.keybuf is None or s.keybuf.numel() < s.bitmap.numel() * 64:
+            s.keybuf = torch.empty(s.bitmap.numel() * 64, dtype=torch.int32, device=self.device)
+        c5 = g.table[:, :BATCH_FIELDS].copy()
+        c5[:, 0] = s.keybuf.data_ptr() + g.table[:, 3] * 256
+        c5[:, 1] = 0
+        return c5
+
+    def _probe(self, s: _Slot, g: _Group, t: _Tables, jn: _JoinRun,
+               bitmap: torch.Tensor) -> tuple:
+        """The probe, the list's last launch (and_dst semantics, its count is
+        the selection's): the fk's batch table and, when an attribute is
+        wanted, the table of the slot's key buffer go up in one copy.  Returns
+        (the selection's bitmap, the latter table on the device or None)."""
+        both = [t.host5(jn.col)]
+        if jn.attr is not None:
+            both.append(self._code_table(s, g))
+        d_j = self._upload(s, np.stack(both))
+        s.keep.append(d_j)
+        d_kout = d_j[1] if jn.attr is not None else None
+        J.probe(jn.dev, jn.code, d_j[0], g.words, bitmap, s.bitmap, s.count,
+                how=J.HOW[jn.how], key_out=d_kout, stream=s.stream)
+        return s.bitmap, d_kout
+
+    def _group_codes(self, s: _Slot, g: _Group, t: _Tables, hs: _HashRun,
+                     bitmap: torch.Tensor) -> tuple:
+        """by=HashBy: find-or-insert of the key column over the bitmap the
+        qualifiers and the probe left; each row's code goes into the slot's
+        key buffer, the accumulate launches' key column.  Returns (the
+        selection's bitmap, the key buffer's table on the device)."""
+        c5 = self._code_table(s, g)
+        # a composite key: every component's table, the join attribute's
+        # being the code buffers' own (the launch runs in place there: a lane
+        # reads its row's components before it stores the row's code); then,
+        # in the same copy, the code buffers'
+        k5 = [t.host5(hs.col)] if hs.cols is None else \
+            [c5 if c is None else t.host5(c) for c in hs.cols]
+        d_h = self._upload(s, np.stack(k5 + [c5]))
+        s.keep.append(d_h)
+        if hs.cols is None:
+            G.group_codes(hs.dev, hs.code, d_h[0], g.words, bitmap, s.bitmap, d_h[1],
+                          stream=s.stream)
+        else:
+            G.group_codes_multi(hs.dev, d_h[:-1], g.words, bitmap, s.bitmap, d_h[-1],
+                                stream=s.stream)
+        return s.bitmap, d_h[-1]
+
+    def _accumulate(self, s: _Slot, g: _Group, t: _Tables, run: _Run, any_col: int,
+                    bitmap: torch.Tensor, key_ptr: int):
+        """The aggregate launches over the selection.  The host's time here
+        delays the next group's read: the columns' batch tables go up in one
+        copy and the launches are one native call.  Returns the entries'
+        arguments when slabs are left for the emit stream to fold."""
+        agg, hs = run.agg, run.hash
+        n = len(g.table)
+        cols = sorted({any_col if c is None else c for c in agg.entry_cols} |
+                      ({agg.key_col} if agg.key_col is not None else set()))
+        d_t5 = self._upload(s, np.stack([t.host5(c) for c in cols]))
+        s.keep.append(d_t5)
+        at = {c: d_t5.data_ptr() + i * n * BATCH_FIELDS * 8 for i, c in enumerate(cols)}
+        if hs is not None:
+            # the accumulate launches add into the table's arrays in HBM:
+            # no slabs, nothing left for the emit stream to fold
+            for e, c in enumerate(agg.entry_cols):
+                hs.dev.args[e].vals = at[any_col if c is None else c]
+            G.group_agg_many(hs.dev, bitmap, g.words, key_ptr, n, stream=s.stream)
+            return None
+        # one aggregate launch per aggregated column on the slot's stream,
+        # each leaving its workgroups' slabs: the slabs are one allocation
+        lay = agg.layout
+        if g.words not in agg.slab_words:
+            agg.slab_words[g.words] = [A.slab_words(lay, e, g.words)
+                                       for e in range(len(lay.entries))]
+        sw = agg.slab_words[g.words]
+        d_slabs = torch.empty(sum(sw), dtype=torch.int64, device=self.device)
+        s.keep.append(d_slabs)
+        args = A.entry_args(lay, run.block)
+        o = d_slabs.data_ptr()
+        for e, c in enumerate(agg.entry_cols):
+            args[e].vals = at[any_col if c is None else c]
+            args[e].slabs = o
+            o += 8 * sw[e]
+        A.agg_many(lay, args, run.block, bitmap, g.words,
+                   at[agg.key_col] if agg.key_col is not None else key_ptr, n, stream=s.stream)
+        return args
+
+    def _emit(self, s: _Slot, g: _Group, run: _Run, d_rows: torch.Tensor,
+              d_proj: Optional[torch.Tensor], args) -> None:
+        """Decode + filter of successive groups overlap on their slots'
+        streams; the row-id emit (+ projection gather) and the fold of the
+        slabs run in group order on one stream (the output cursor and the
+        block are shared), which then frees the slot."""
         ready = torch.cuda.Event()
-        ready.record(cs)
+        ready.record(s.stream)
         es = self.emit_stream
         es.wait_event(ready)
         with torch.cuda.stream(es):
-            if agg is not None:
+            if args is not None:
                 # the slabs into the scan's accumulator block, in group order
-                if hs is None:
-                    A.agg_reduce_many(agg.layout, args, g.words, stream=es)
-            elif pstr:
-                bitmap_to_rows_str(s.bitmap, g.words, d_rows, state["out"], state["cursor"],
-                                   d_proj, state["owidth"], state["poff"], state["pchars"],
-                                   state["ccursor"], pvalid=state.get("pvalid"), stream=es)
-            else:
-                bitmap_to_rows(s.bitmap, g.words, d_rows, state["out"], state["cursor"],
-                               stream=es, proj=d_proj, proj_out=state.get("pout"),
-                               proj_valid=state.get("pvalid"))
-            state["count"] += s.count
+                A.agg_reduce_many(run.agg.layout, args, g.words, stream=es)
+            if run.pchars is not None:
+                bitmap_to_rows_str(s.bitmap, g.words, d_rows, run.out, run.cursor, d_proj,
+                                   run.owidth, run.poff, run.pchars, run.ccursor,
+                                   pvalid=run.pvalid, stream=es)
+            elif run.out is not None:
+                bitmap_to_rows(s.bitmap, g.words, d_rows, run.out, run.cursor, stream=es,
+                               proj=d_proj, proj_out=run.pout, proj_valid=run.pvalid)
+            run.count += s.count
             s.count.zero_()
-            if descs is not None:
-                state["err"] += s.err
+            if g.descs is not None or g.descs_lanes is not None:
+                run.err += s.err
                 s.err.zero_()
             s.event = torch.cuda.Event()
             s.event.record(es)
-        state["bytes_read"] += g.read_bytes
-        state["column_bytes"] += g.column_bytes
-        state["marks"].append((k, "launched", time.perf_counter()))
 
     # ------------------------------------------------------------- query
     def dictionary(self, name: str):
         """Decoded dictionary of a dictionary-encoded column (host, cached):
         (values, valid) as utils.arrow_ipc.dictionary_values returns them."""
-        if name not in self._dicts:
-            col = self.meta.schema[self.meta.column_index(name)]
-            self._dicts[name] = dictionary_values(self.meta, col, self.path)
-        return self._dicts[name]
+        return _dictionary(self.meta, self.path, self._dicts, name)
 
     def _compile(self, p: Pred) -> Compiled:
         key = (p.col, p.op, repr(p.value))
         if key not in self._compiled:
             col = self.meta.schema[self.meta.column_index(p.col)]
-            dic = self.dictionary(p.col) if (col.dictionary is not None and
-                                             p.op not in ("is_null", "is_valid")) else None
-            self._compiled[key] = compile_pred(p, col, dic)
+            self._compiled[key] = _compile_pred(p, col, self.dictionary)
         return self._compiled[key]
 
     def _join_run(self, join: Join, names: List[str], attr: Optional[JoinAttr]) -> _JoinRun:
@@ -1179,6 +1223,69 @@ class ArrowScan:
         name = attr.name if attr is not None else None
         return _JoinRun(names.index(join.col), J.FK_CODE[col.storage], join.how,
                         join.table._device_table(name), name)
+
+    def _resolve(self, names: List[str], batches: Optional[Tuple[int, int]]) -> tuple:
+        """(Column metas, rows, groups) of a scan of ``names`` over ``batches``,
+        planned once per object.  No names: the footer's rows, nothing to read."""
+        nb = self.meta.nbatches
+        rng = (0, nb) if batches is None else (max(0, int(batches[0])), min(nb, int(batches[1])))
+        if not names:
+            return [], int(np.asarray(self.meta.rows)[rng[0]:max(rng[0], rng[1])].sum()), []
+        key = (tuple(names), rng)
+        if key not in self._plans:                # the file's layout is fixed once opened
+            if tuple(names) not in self._bplans:
+                self._bplans[tuple(names)] = self._plan(names)
+            allb, cols, _ = self._bplans[tuple(names)]
+            sel = allb[rng[0]:max(rng[0], rng[1])]
+            self._plans[key] = (cols, int(sel.rows.sum()) if len(sel) else 0, self._groups(sel))
+        return self._plans[key]
+
+    def _zero(self) -> torch.Tensor:
+        return torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def _emit_stream(self) -> torch.cuda.Stream:
+        # one emit stream per scan object (its library-kept scratch follows it)
+        if getattr(self, "emit_stream", None) is None:
+            self.emit_stream = torch.cuda.Stream(device=self.device)
+        return self.emit_stream
+
+    def _drive(self, groups: List[_Group], spec, run: _Run) -> float:
+        """Every group through the slot ring, then the scan's one sync.
+        Returns the clock before the first submit."""
+        self._ensure_slots(groups)
+        self._emit_stream()
+        t_start = time.perf_counter()
+
+        def submit(k: int) -> None:
+            self._submit(k, groups[k])
+            run.marks.append((k, "submitted", time.perf_counter()))
+        # depth nslots - 1 of reads ahead of the group being computed
+        ahead = max(1, min(self.nslots, len(self._slots)) - 1)
+        for k in range(min(ahead, len(groups))):
+            submit(k)
+        for k in range(len(groups)):
+            if run.block_ready is not None:
+                # the aggregate launches (slot streams) count malformed keys
+                # in the block: they must see it initialised
+                self._slots[k % len(self._slots)].stream.wait_event(run.block_ready)
+            self._compute(k, spec, run)
+            if k + ahead < len(groups):
+                submit(k + ahead)
+        torch.cuda.synchronize(self.device)
+        # whatever the scan's outcome, no slot keeps its tensors and events
+        for s in self._slots:
+            s.keep, s.event = [], None
+        return t_start
+
+    def _check_decoded(self, err: int, names: List[str]) -> None:
+        if err:
+            raise RuntimeError(f"{'ZSTD' if self._codec == D.ARROW_ZSTD else 'LZ4'} decode "
+                               f"failed for {err} buffer(s) of columns {names}")
+
+    @staticmethod
+    def _seconds(run: _Run, t0: float, t_plan: float, t_alloc: float) -> dict:
+        return {"plan_s": t_plan - t0, "alloc_s": t_alloc - t_plan, "wait_s": run.wait_s,
+                "total_s": time.perf_counter() - t0}
 
     def scan_where(self, quals, project=None, batches: Optional[Tuple[int, int]] = None,
                    join: Optional[Join] = None) -> ScanOut:
@@ -1210,21 +1317,8 @@ class ArrowScan:
             project = None
         cl = clauses(quals) if (quals or join is None) else []
         t0 = time.perf_counter()
-        names: List[str] = []
-        for n in [p.col for c in cl for p in c] + ([join.col] if join else []) + \
-                ([project] if project else []):
-            if n not in names:
-                names.append(n)
-        nb = self.meta.nbatches
-        rng = (0, nb) if batches is None else (max(0, int(batches[0])), min(nb, int(batches[1])))
-        key = (tuple(names), rng)
-        if key not in self._plans:                # the file's layout is fixed once opened
-            if tuple(names) not in self._bplans:
-                self._bplans[tuple(names)] = self._plan(names)
-            allb, cols, _ = self._bplans[tuple(names)]
-            sel = allb[rng[0]:max(rng[0], rng[1])]
-            self._plans[key] = (cols, int(sel.rows.sum()) if len(sel) else 0, self._groups(sel))
-        cols, nrows, groups = self._plans[key]
+        names = _scanned(cl, join, [project] if project else [])
+        cols, nrows, groups = self._resolve(names, batches)
         spec = [[(names.index(p.col), self._compile(p)) for p in c] for c in cl]
         t_plan = time.perf_counter()
         out = torch.empty(max(nrows, 1), dtype=torch.int64, device=self.device)
@@ -1258,53 +1352,28 @@ class ArrowScan:
                            values=pout[:0] if pout is not None else
                            (pchars[:0] if pchars is not None else None),
                            column=pmeta, dictionary=pdict,
-                           offsets=torch.zeros(1, dtype=torch.int64, device=self.device)
-                           if pstrings else None)
-        self._ensure_slots(groups)
-        # one emit stream per scan object (its library-kept scratch follows it)
-        if getattr(self, "emit_stream", None) is None:
-            self.emit_stream = torch.cuda.Stream(device=self.device)
-        z = lambda: torch.zeros(1, dtype=torch.int64, device=self.device)
-        state = dict(out=out, cursor=z(), count=z(), err=z(), wait_s=0.0, bytes_read=0,
-                     column_bytes=0, pout=pout, pvalid=pvalid, pchars=pchars, poff=poff,
-                     ccursor=z(), owidth=8 if pstrings and pmeta.large else 4, marks=[])
+                           offsets=self._zero() if pstrings else None)
+        run = _Run(self._zero(), self._zero(), out=out, cursor=self._zero(),
+                   ccursor=self._zero(), pout=pout, pvalid=pvalid, pchars=pchars, poff=poff,
+                   owidth=8 if pstrings and pmeta.large else 4, pattr=pattr is not None,
+                   pcol=pcol)
         if join is not None:
-            state["join"] = self._join_run(join, names, pattr)
-            state["pattr"] = pattr is not None
-        t_alloc = time.perf_counter()
-        # depth nslots - 1 of reads ahead of the group being computed
-        ahead = max(1, min(self.nslots, len(self._slots)) - 1)
-        for k in range(min(ahead, len(groups))):
-            self._submit(k, groups[k])
-            state["marks"].append((k, "submitted", time.perf_counter()))
-        for k in range(len(groups)):
-            self._compute(k, spec, pcol, state)
-            if k + ahead < len(groups):
-                self._submit(k + ahead, groups[k + ahead])
-                state["marks"].append((k + ahead, "submitted", time.perf_counter()))
-        torch.cuda.synchronize(self.device)
-        cursor, count, err, nchars = torch.cat([state["cursor"], state["count"], state["err"],
-                                                state["ccursor"]]).tolist()
-        t_end = time.perf_counter()
-        if err:
-            raise RuntimeError(f"{'ZSTD' if self._codec == D.ARROW_ZSTD else 'LZ4'} decode "
-                               f"failed for {err} buffer(s) of columns {names}")
+            run.join = self._join_run(join, names, pattr)
+        t_alloc = self._drive(groups, spec, run)
+        cursor, count, err, nchars = torch.cat([run.cursor, run.count, run.err,
+                                                run.ccursor]).tolist()
+        secs = self._seconds(run, t0, t_plan, t_alloc)
+        self._check_decoded(err, names)
         if cursor != count:
             raise RuntimeError(f"row emit mismatch: {cursor} ids for {count} selected")
-        for s in self._slots:
-            s.keep = []
-            s.event = None
         offsets = None
         if pstrings:
             poff[count] = nchars
             offsets = poff[:count + 1]
-        return ScanOut(nrows, int(count), out[:count],
-                       {"plan_s": t_plan - t0, "alloc_s": t_alloc - t_plan,
-                        "wait_s": state["wait_s"], "total_s": t_end - t0,
-                        # per group: (group, event, ms since the scan's first submit)
-                        "timeline_ms": [(k, e, round((t - t_alloc) * 1e3, 3))
-                                        for k, e, t in state["marks"]]},
-                       bytes_read=state["bytes_read"], column_bytes=state["column_bytes"],
+        # per group: (group, event, ms since the scan's first submit)
+        secs["timeline_ms"] = [(k, e, round((t - t_alloc) * 1e3, 3)) for k, e, t in run.marks]
+        return ScanOut(nrows, int(count), out[:count], secs,
+                       bytes_read=run.bytes_read, column_bytes=run.column_bytes,
                        groups=len(groups),
                        values=pout[:count] if pout is not None else
                        (pchars[:nchars] if pchars is not None else None),
@@ -1353,110 +1422,63 @@ class ArrowScan:
             by = None
         cl = clauses(quals) if quals else []
         agg = _agg_spec(self.meta, aggs, by, self.dictionary, battr, hb)
-        names: List[str] = []
-        for n in [p.col for c in cl for p in c] + ([join.col] if join else []) + agg.names:
-            if n not in names:
-                names.append(n)
-        nb = self.meta.nbatches
-        rng = (0, nb) if batches is None else (max(0, int(batches[0])), min(nb, int(batches[1])))
+        names = _scanned(cl, join, agg.names)
+        cols, nrows, groups = self._resolve(names, batches)
         if not names:
             # count(*) of everything: the footer answers
             block = A.new_block(agg.layout)
-            nrows = int(np.asarray(self.meta.rows)[rng[0]:max(rng[0], rng[1])].sum())
             block[agg.layout.pos(0, A.COUNT)] = np.uint64(nrows)
             return _agg_out(agg, block, nrows, {"total_s": time.perf_counter() - t0})
-        key = (tuple(names), rng)
-        if key not in self._plans:
-            if tuple(names) not in self._bplans:
-                self._bplans[tuple(names)] = self._plan(names)
-            allb, cols, _ = self._bplans[tuple(names)]
-            sel = allb[rng[0]:max(rng[0], rng[1])]
-            self._plans[key] = (cols, int(sel.rows.sum()) if len(sel) else 0, self._groups(sel))
-        cols, nrows, groups = self._plans[key]
         spec = [[(names.index(p.col), self._compile(p)) for p in c] for c in cl]
         t_plan = time.perf_counter()
-        if hb is not None and (not groups or nrows == 0):
-            return _hash_out(agg, G.empty_groups(agg.layout.entries, agg.hash_unsigned,
-                                                 agg.keyspec), nrows,
-                             {"total_s": time.perf_counter() - t0})
         if not groups or nrows == 0:
-            return _agg_out(agg, A.new_block(agg.layout), nrows,
-                            {"total_s": time.perf_counter() - t0})
+            secs = {"total_s": time.perf_counter() - t0}
+            if hb is None:
+                return _agg_out(agg, A.new_block(agg.layout), nrows, secs)
+            return _hash_out(agg, G.empty_groups(agg.layout.entries, agg.hash_unsigned,
+                                                 agg.keyspec), nrows, secs)
         agg.entry_cols = [None if n is None else names.index(n) for n in agg.entry_names]
         # by=dim[attr]: no file column, the key is the probe's code buffer
         agg.key_col = names.index(by) if by is not None else None
-        self._ensure_slots(groups)
-        if getattr(self, "emit_stream", None) is None:
-            self.emit_stream = torch.cuda.Stream(device=self.device)
-        z = lambda: torch.zeros(1, dtype=torch.int64, device=self.device)
+        run = _Run(self._zero(), self._zero(), agg=agg)
+        if join is not None:
+            run.join = self._join_run(join, names, battr if hb is None else hb.attr)
         # the block is initialised on the emit stream, where the reduces follow
-        with torch.cuda.stream(self.emit_stream):
-            block = A.alloc_block(agg.layout, self.device, stream=self.emit_stream)
+        es = self._emit_stream()
+        with torch.cuda.stream(es):
+            run.block = A.alloc_block(agg.layout, self.device, stream=es)
             dev = None
             if hb is not None:
                 # the table and its accumulators, initialised before any
                 # launch can see a slot (block_ready below)
                 dev = G.DeviceGroups(agg.layout.entries, hb.groups, self.device,
-                                     agg.hash_unsigned, stream=self.emit_stream,
-                                     spec=agg.keyspec)
-        state = dict(agg=agg, block=block, count=z(), err=z(), wait_s=0.0, bytes_read=0,
-                     column_bytes=0, marks=[])
-        if join is not None:
-            state["join"] = self._join_run(join, names, battr if hb is None else hb.attr)
+                                     agg.hash_unsigned, stream=es, spec=agg.keyspec)
         if agg.keyspec is not None:
-            state["hash"] = _HashRun(-1, 0, dev, [None if isinstance(c, JoinAttr) else
-                                                  names.index(c) for c in hb.comps])
+            run.hash = _HashRun(-1, 0, dev, [None if isinstance(c, JoinAttr) else
+                                             names.index(c) for c in hb.comps])
         elif hb is not None:
             kc = self.meta.schema[self.meta.column_index(hb.col)]
-            state["hash"] = _HashRun(names.index(hb.col), G.KEY_CODE[kc.storage], dev)
-        # the aggregate launches (slot streams) count malformed keys in the
-        # block: they must see it initialised
-        ready = torch.cuda.Event()
-        ready.record(self.emit_stream)
-        state["block_ready"] = ready
-        t_alloc = time.perf_counter()
-        ahead = max(1, min(self.nslots, len(self._slots)) - 1)
-        for k in range(min(ahead, len(groups))):
-            self._submit(k, groups[k])
-        for k in range(len(groups)):
-            self._slots[k % len(self._slots)].stream.wait_event(ready)
-            self._compute(k, spec, None, state)
-            if k + ahead < len(groups):
-                self._submit(k + ahead, groups[k + ahead])
+            run.hash = _HashRun(names.index(hb.col), G.KEY_CODE[kc.storage], dev)
+        run.block_ready = torch.cuda.Event()
+        run.block_ready.record(es)
+        t_alloc = self._drive(groups, spec, run)
         if dev is not None:
             # behind the last group on the emit stream: the occupied slots
             # and the two reserved codes, compacted; only they and the header
             # are read back
-            with torch.cuda.stream(self.emit_stream):
+            with torch.cuda.stream(es):
                 hdr, found = G.compact(dev)
-        torch.cuda.synchronize(self.device)
-        err = int(state["err"].item())
-        host = A.block_to_host(block)
-        t_end = time.perf_counter()
-        for s in self._slots:
-            s.keep = []
-            s.event = None
-        if err:
-            raise RuntimeError(f"{'ZSTD' if self._codec == D.ARROW_ZSTD else 'LZ4'} decode "
-                               f"failed for {err} buffer(s) of columns {names}")
-        secs = {"plan_s": t_plan - t0, "alloc_s": t_alloc - t_plan,
-                "wait_s": state["wait_s"], "total_s": t_end - t0}
-        if dev is not None:
-            nk, over = int(hdr[G.H_NKEYS]), int(hdr[G.H_OVERFLOW])
-            if nk > hb.groups or over:
-                seen = f"{nk} distinct keys seen" if not over else \
-                    f"the table is full ({nk} keys in it, {over} selected row(s) found no slot)"
-                raise RuntimeError(f"GROUP BY HashBy({hb.col!r}): more than groups={hb.groups} "
-                                   f"distinct keys: {seen}; scan again with a larger groups=")
-            if agg.keyspec is not None:
-                _check_range(agg.keyspec, hdr[G.H_RANGE:G.H_RANGE + len(agg.keyspec)])
-            return _hash_out(agg, found, nrows, secs, bytes_read=state["bytes_read"],
-                             column_bytes=state["column_bytes"], groups=len(groups))
-        return _agg_out(agg, host, nrows,
-                        {"plan_s": t_plan - t0, "alloc_s": t_alloc - t_plan,
-                         "wait_s": state["wait_s"], "total_s": t_end - t0},
-                        bytes_read=state["bytes_read"], column_bytes=state["column_bytes"],
-                        groups=len(groups))
+        err = int(run.err.item())
+        host = A.block_to_host(run.block)
+        secs = self._seconds(run, t0, t_plan, t_alloc)
+        self._check_decoded(err, names)
+        moved = dict(bytes_read=run.bytes_read, column_bytes=run.column_bytes, groups=len(groups))
+        if dev is None:
+            return _agg_out(agg, host, nrows, secs, **moved)
+        _check_groups(hb, int(hdr[G.H_NKEYS]), int(hdr[G.H_OVERFLOW]))
+        if agg.keyspec is not None:
+            _check_range(agg.keyspec, hdr[G.H_RANGE:G.H_RANGE + len(agg.keyspec)])
+        return _hash_out(agg, found, nrows, secs, **moved)
 
     def host_aggregate(self, quals, aggs, by=None, batches: Optional[Tuple[int, int]] = None,
                        join: Optional[Join] = None) -> "AggOut":
@@ -1515,6 +1537,81 @@ def _host_join(join: Join, v, ok, m: np.ndarray):
     return (m & ~match if join.how == "anti" else m & match), row
 
 
+def _scanned(cl, join: Optional[Join], more: Sequence[str]) -> List[str]:
+    """The columns a scan reads, each once: the qualifiers', the foreign key,
+    then ``more`` — the order of the plan's columns."""
+    return list(dict.fromkeys([p.col for c in cl for p in c] + ([join.col] if join else []) +
+                              list(more)))
+
+
+def _dictionary(meta: ArrowFile, path: str, dicts: dict, name: str):
+    """Decoded dictionary of a dictionary-encoded column, cached in ``dicts``."""
+    if name not in dicts:
+        dicts[name] = dictionary_values(meta, meta.schema[meta.column_index(name)], path)
+    return dicts[name]
+
+
+def _compile_pred(p: Pred, col: Column, dictionary) -> Compiled:
+    """compile_pred with the column's dictionary (``dictionary(name)``) where
+    the predicate looks at values: a null test needs none."""
+    dic = dictionary(p.col) if (col.dictionary is not None and
+                                p.op not in ("is_null", "is_valid")) else None
+    return compile_pred(p, col, dic)
+
+
+def _host_batches(path: str, meta: ArrowFile, dicts: dict, cl, join: Optional[Join],
+                  more: Sequence[str], batches: Optional[Tuple[int, int]],
+                  values=lambda name: True):
+    """The host twins' scan: per record batch of the range (batch index,
+    batch, {column: (values, validity)}, the rows the CNF ``cl`` and the join
+    select, the join's build row per row or None).  The qualifier and join
+    columns and ``more`` are read and decoded; a column of ``more`` for which
+    ``values(name)`` is false gets its validity alone (values None)."""
+    schema = {c.name: (i, c) for i, c in enumerate(meta.schema)}
+    dictionary = lambda name: _dictionary(meta, path, dicts, name)
+    comp = []
+    for c in cl:
+        for p in c:
+            if p.col not in schema:
+                raise ValueError(f"no column {p.col!r}")
+        comp.append([(p.col, _compile_pred(p, schema[p.col][1], dictionary)) for p in c])
+    must = set(_scanned(cl, join, []))
+    nb = meta.nbatches
+    b0, b1 = (0, nb) if batches is None else (max(0, batches[0]), min(nb, batches[1]))
+    src = _Src(path)
+    try:
+        for bi in range(b0, b1):
+            b = meta.batches[bi]
+            data = {}
+            for n in sorted(must | set(more)):
+                ci, col = schema[n]
+                ch = b.columns[ci]
+                vraw = read_buffer(src, ch.validity, b.codec) if ch.null_count else b""
+                ok = validity_bits(vraw, ch.length)
+                if n not in must and not values(n):
+                    data[n] = (None, ok)
+                    continue
+                d = read_buffer(src, ch.data, b.codec)
+                vcol = col if col.dictionary is None else Column(n, "int", col.dictionary.index_bits,
+                                                                 col.dictionary.index_signed)
+                x = read_buffer(src, ch.extra, b.codec) if (ch.extra is not None and
+                                                            col.dictionary is None) else b""
+                data[n] = (decode_values(vcol, ch.length, d, x), ok)
+            m = np.ones(b.length, bool)
+            for c in comp:
+                cm = np.zeros(b.length, bool)
+                for name, cq in c:
+                    v, ok = data[name]
+                    cm |= evaluate(cq, v, ok, b.length)
+                m &= cm
+            jrow = None
+            if join is not None:
+                m, jrow = _host_join(join, *data[join.col], m)
+            yield bi, b, data, m, jrow
+    finally:
+        src.close()
+
+
 def host_scan_where(path: str, quals, project=None,
                     batches: Optional[Tuple[int, int]] = None, meta: Optional[ArrowFile] = None,
                     dicts: Optional[dict] = None, join: Optional[Join] = None) -> HostScanOut:
@@ -1529,70 +1626,27 @@ def host_scan_where(path: str, quals, project=None,
     if pattr is not None:
         project = None
     cl = clauses(quals) if (quals or join is None) else []
-    schema = {c.name: (i, c) for i, c in enumerate(meta.schema)}
-
-    def dictionary(name):
-        if name not in dicts:
-            dicts[name] = dictionary_values(meta, schema[name][1], path)
-        return dicts[name]
-    comp = []
-    for c in cl:
-        row = []
-        for p in c:
-            col = schema[p.col][1]
-            dic = dictionary(p.col) if col.dictionary is not None and \
-                p.op not in ("is_null", "is_valid") else None
-            row.append((p.col, compile_pred(p, col, dic)))
-        comp.append(row)
-    names = sorted({n for c in comp for n, _ in c} | ({project} if project else set()) |
-                   ({join.col} if join else set()))
-    nb = meta.nbatches
-    b0, b1 = (0, nb) if batches is None else (max(0, batches[0]), min(nb, batches[1]))
     base = np.concatenate([[0], np.cumsum(meta.rows)]).astype(np.int64)
+    nrows = 0
     ids, vals, valid = [], [], []
-    src = _Src(path)
-    try:
-        for bi in range(b0, b1):
-            b = meta.batches[bi]
-            data = {}
-            for n in names:
-                ci, col = schema[n]
-                ch = b.columns[ci]
-                vraw = read_buffer(src, ch.validity, b.codec) if ch.null_count else b""
-                d = read_buffer(src, ch.data, b.codec)
-                vcol = col if col.dictionary is None else Column(n, "int", col.dictionary.index_bits,
-                                                                 col.dictionary.index_signed)
-                x = read_buffer(src, ch.extra, b.codec) if (ch.extra is not None and
-                                                            col.dictionary is None) else b""
-                data[n] = (decode_values(vcol, ch.length, d, x), validity_bits(vraw, ch.length))
-            n = b.length
-            m = np.ones(n, bool)
-            for c in comp:
-                cm = np.zeros(n, bool)
-                for name, cq in c:
-                    v, ok = data[name]
-                    cm |= evaluate(cq, v, ok, n)
-                m &= cm
-            if join is not None:
-                m, jrow = _host_join(join, *data[join.col], m)
-            sel = np.flatnonzero(m)
-            ids.append(sel + base[bi])
-            if pattr is not None:
-                vals.append(pattr.codes[jrow[sel]] if len(pattr.codes) else
-                            np.zeros(0, np.int32))
-                valid.append(np.ones(len(sel), bool))
-            if project:
-                v, ok = data[project]
-                if isinstance(v, tuple):
-                    offs, chars = v
-                    vals.append([chars[offs[i]:offs[i + 1]].tobytes() for i in sel])
-                else:
-                    vals.append(np.asarray(v)[sel])
-                valid.append(ok[sel] if ok is not None else np.ones(len(sel), bool))
-    finally:
-        src.close()
-    out = HostScanOut(int(base[b1] - base[b0]) if b1 > b0 else 0,
-                      np.concatenate(ids) if ids else np.zeros(0, np.int64))
+    for bi, b, data, m, jrow in _host_batches(path, meta, dicts, cl, join,
+                                              [project] if project else [], batches):
+        nrows += b.length
+        sel = np.flatnonzero(m)
+        ids.append(sel + base[bi])
+        if pattr is not None:
+            vals.append(pattr.codes[jrow[sel]] if len(pattr.codes) else
+                        np.zeros(0, np.int32))
+            valid.append(np.ones(len(sel), bool))
+        if project:
+            v, ok = data[project]
+            if isinstance(v, tuple):
+                offs, chars = v
+                vals.append([chars[offs[i]:offs[i + 1]].tobytes() for i in sel])
+            else:
+                vals.append(np.asarray(v)[sel])
+            valid.append(ok[sel] if ok is not None else np.ones(len(sel), bool))
+    out = HostScanOut(nrows, np.concatenate(ids) if ids else np.zeros(0, np.int64))
     if pattr is not None:
         out.dictionary = pattr.values
     if project or pattr is not None:
@@ -1653,12 +1707,37 @@ def _check_range(spec: G.KeySpec, misfit) -> None:
                                f"bits={{{c.name!r}: n}}")
 
 
+def _check_groups(hb: HashBy, nkeys: int, overflow: int = 0) -> None:
+    """Raise for a scan that met more distinct keys than ``hb.groups`` (or
+    whose table had no slot left for ``overflow`` selected rows)."""
+    if nkeys > hb.groups or overflow:
+        seen = f"{nkeys} distinct keys seen" if not overflow else \
+            f"the table is full ({nkeys} keys in it, {overflow} selected row(s) found no slot)"
+        raise RuntimeError(f"GROUP BY HashBy({hb.col!r}): more than groups={hb.groups} "
+                           f"distinct keys: {seen}; scan again with a larger groups=")
+
+
+def _hash_key(schema: dict, name: str, shown: str, others: str = "") -> Column:
+    """The column ``name`` as a HashBy key (``shown`` in the error's text,
+    ``others``: where the refused kinds are grouped instead)."""
+    if name not in schema:
+        raise ValueError(f"no column {name!r}")
+    k = schema[name]
+    if k.dictionary is not None or k.kind not in ("int",) + _TEMPORAL or \
+            k.storage not in G.KEY_CODE:
+        kind = "dictionary-encoded" if k.dictionary is not None else k.kind
+        raise NotImplementedError(
+            f"GROUP BY HashBy({shown}): {kind} keys (integer and date / time / timestamp / "
+            f"duration columns are hashed{others})")
+    return k
+
+
 def _key_spec(meta: ArrowFile, hb: HashBy) -> Tuple[G.KeySpec, list]:
     """The KeySpec of by=HashBy([...]) against the schema, and per component
     its join attribute's values (None for a column).  A column is nullable if
     any record batch of the file has nulls in it — the whole file, whatever
     range is scanned, so that results of its ranges pack alike and merge."""
-    schema = {c.name: (i, c) for i, c in enumerate(meta.schema)}
+    schema = {c.name: c for c in meta.schema}
     comps, attrs = [], []
     for c in hb.comps:
         if isinstance(c, JoinAttr):
@@ -1668,15 +1747,8 @@ def _key_spec(meta: ArrowFile, hb: HashBy) -> Tuple[G.KeySpec, list]:
             comps.append((c.name, "u4", max(1, int(nv - 1).bit_length()), False))
             attrs.append(list(c.values))
             continue
-        if c not in schema:
-            raise ValueError(f"no column {c!r}")
-        ci, k = schema[c]
-        if k.dictionary is not None or k.kind not in ("int",) + _TEMPORAL or \
-                k.storage not in G.KEY_CODE:
-            kind = "dictionary-encoded" if k.dictionary is not None else k.kind
-            raise NotImplementedError(
-                f"GROUP BY HashBy(..., {c}, ...): {kind} keys (integer and date / time / "
-                "timestamp / duration columns are hashed)")
+        k = _hash_key(schema, c, f"..., {c}, ...")
+        ci = meta.column_index(c)
         nullable = bool(meta.nbatches) and bool(np.any(np.asarray(meta.columns[ci].null_count)))
         comps.append((c, k.storage, hb.bits.get(c), nullable))
         attrs.append(None)
@@ -1743,23 +1815,13 @@ def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary,
                 "or temporal column of any width)")
         nslots = len(keyvals) + 1
     keyspec = key_attrs = None
+    if hb is not None and jattr is not None:
+        raise ValueError("by=: a JoinTable attribute or HashBy, not both")
     if hb is not None and hb.comps is not None:
-        if jattr is not None:
-            raise ValueError("by=: a JoinTable attribute or HashBy, not both")
         keyspec, key_attrs = _key_spec(meta, hb)
     elif hb is not None:
-        if jattr is not None:
-            raise ValueError("by=: a JoinTable attribute or HashBy, not both")
-        if hb.col not in schema:
-            raise ValueError(f"no column {hb.col!r}")
-        k = schema[hb.col]
-        if k.dictionary is not None or k.kind not in ("int",) + _TEMPORAL or \
-                k.storage not in G.KEY_CODE:
-            kind = "dictionary-encoded" if k.dictionary is not None else k.kind
-            raise NotImplementedError(
-                f"GROUP BY HashBy({hb.col}): {kind} keys (integer and date / time / timestamp / "
-                "duration columns are hashed; dictionary-encoded, bool and 8-bit columns are "
-                "grouped by name)")
+        _hash_key(schema, hb.col, hb.col, "; dictionary-encoded, bool and 8-bit columns are "
+                                          "grouped by name")
     if jattr is not None:
         # the key column is the probe's int32 code buffer; every selected row
         # matched, so the null slot stays empty (the kernels want two slots)
@@ -1773,19 +1835,14 @@ def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary,
     names = [n for n in entry_names[1:]]
     if by is not None and by not in names:
         names.append(by)
-    if keyspec is not None:
-        for c in hb.comps:
+    if hb is not None:
+        for c in [hb.col] if keyspec is None else hb.comps:
             if not isinstance(c, JoinAttr) and c not in names:
                 names.append(c)
         return _AggSpec(aggs, hb.col, A.Layout(entries), entry_names, names,
-                        {n: schema[n] for n in names}, None, hashed=True, hash_unsigned=True,
-                        keyspec=keyspec, key_attrs=key_attrs)
-    if hb is not None:
-        if hb.col not in names:
-            names.append(hb.col)
-        return _AggSpec(aggs, hb.col, A.Layout(entries), entry_names, names,
                         {n: schema[n] for n in names}, None, hashed=True,
-                        hash_unsigned=schema[hb.col].storage[0] == "u")
+                        hash_unsigned=keyspec is not None or schema[hb.col].storage[0] == "u",
+                        keyspec=keyspec, key_attrs=key_attrs)
     return _AggSpec(aggs, by if jattr is None else jattr.name,
                     A.Layout(entries, nslots, key_code), entry_names, names,
                     {n: schema[n] for n in names}, keyvals, join_attr=jattr is not None)
@@ -1937,7 +1994,6 @@ def _hash_out(spec: _AggSpec, found: G.Groups, rows: int, seconds: Dict[str, flo
             cols.append((v, ok))
         # a million tuples: the cyclic collector would walk them again and
         # again while the list grows (half the time of this step)
-        import gc
         paused = gc.isenabled()
         gc.disable()
         try:
@@ -1960,116 +2016,58 @@ def host_aggregate(path: str, quals, aggs, by=None,
     meta = meta if meta is not None else read_metadata(path)
     dicts = dicts if dicts is not None else {}
     cl = clauses(quals) if quals else []
-    schema = {c.name: (i, c) for i, c in enumerate(meta.schema)}
-
-    def dictionary(name):
-        if name not in dicts:
-            dicts[name] = dictionary_values(meta, schema[name][1], path)
-        return dicts[name]
     battr = by if isinstance(by, JoinAttr) else None
     hb = by if isinstance(by, HashBy) else None
-    hattr = hb.attr if hb is not None else None
-    join = _check_join(meta, join, battr if hb is None else hattr)
+    join = _check_join(meta, join, battr if hb is None else hb.attr)
     if battr is not None or hb is not None:
         by = None
-    spec = _agg_spec(meta, aggs, by, dictionary, battr, hb)
+    spec = _agg_spec(meta, aggs, by, lambda name: _dictionary(meta, path, dicts, name), battr, hb)
     found = G.empty_groups(spec.layout.entries, spec.hash_unsigned, spec.keyspec) \
         if hb is not None else None
     misfit = np.zeros(G.MAX_KEYS, np.int64)
-    comp = []
-    for c in cl:
-        row = []
-        for p in c:
-            if p.col not in schema:
-                raise ValueError(f"no column {p.col!r}")
-            col = schema[p.col][1]
-            dic = dictionary(p.col) if col.dictionary is not None and \
-                p.op not in ("is_null", "is_valid") else None
-            row.append((p.col, compile_pred(p, col, dic)))
-        comp.append(row)
-    names = sorted({n for c in comp for n, _ in c} | set(spec.names) |
-                   ({join.col} if join else set()))
-    nb = meta.nbatches
-    b0, b1 = (0, nb) if batches is None else (max(0, batches[0]), min(nb, batches[1]))
     lay = spec.layout
     block = A.new_block(lay)
     nrows = 0
-    src = _Src(path)
-    try:
-        for bi in range(b0, b1):
-            b = meta.batches[bi]
-            data = {}
-            for n in names:
-                ci, col = schema[n]
-                ch = b.columns[ci]
-                vraw = read_buffer(src, ch.validity, b.codec) if ch.null_count else b""
-                ok = validity_bits(vraw, ch.length)
-                if not any(n == q for c in comp for q, _ in c) and n != by and \
-                        not (join and n == join.col) and \
-                        not (hb and (n == hb.col or n in (hb.comps or ()))) and \
-                        lay.entries[spec.entry_names.index(n)].dtype is None:
-                    data[n] = (None, ok)          # counted only: its validity is enough
-                    continue
-                d = read_buffer(src, ch.data, b.codec)
-                vcol = col if col.dictionary is None else Column(n, "int", col.dictionary.index_bits,
-                                                                 col.dictionary.index_signed)
-                x = read_buffer(src, ch.extra, b.codec) if (ch.extra is not None and
-                                                            col.dictionary is None) else b""
-                data[n] = (decode_values(vcol, ch.length, d, x), ok)
-            n = b.length
-            nrows += n
-            m = np.ones(n, bool)
-            for c in comp:
-                cm = np.zeros(n, bool)
-                for name, cq in c:
-                    v, ok = data[name]
-                    cm |= evaluate(cq, v, ok, n)
-                m &= cm
-            key = None
-            if join is not None:
-                m, jrow = _host_join(join, *data[join.col], m)
-                if battr is not None:
-                    key = (np.where(m, battr.codes[jrow] if len(battr.codes) else 0, 0)
-                           .astype(np.int32), None)
-            if by is not None:
-                kv, kok = data[by]
-                kv = np.asarray(kv)
-                if kv.dtype == np.int8 and schema[by][1].dictionary is None:
-                    kv = kv.view(np.uint8)        # 8-bit key: the slot is the byte
-                key = (kv, kok)
-            ecols = [(None, None) if name is None else data[name] for name in spec.entry_names]
-            if spec.keyspec is not None:
-                # the composite path's twin: packed by the same KeySpec
-                kcols, koks = [], []
-                for c in hb.comps:
-                    if isinstance(c, JoinAttr):
-                        kcols.append(np.where(m, c.codes[jrow] if len(c.codes) else 0, 0)
-                                     .astype(np.uint32))
-                        koks.append(None)
-                    else:
-                        kcols.append(np.asarray(data[c][0]))
-                        koks.append(data[c][1])
-                part, bad = G.host_group_agg_multi(lay.entries, m, spec.keyspec, kcols, koks, ecols)
-                found = G.merge(found, part)
-                misfit[:len(bad)] += bad
-                continue
-            if hb is not None:
-                # the hash path's twin: this batch's groups, united by key
-                kv, kok = data[hb.col]
-                found = G.merge(found, G.host_group_agg(
-                    lay.entries, m, kv, kok,
-                    [(None, None) if name is None else data[name] for name in spec.entry_names]))
-                continue
-            for e, name in enumerate(spec.entry_names):
-                v, ok = (None, None) if name is None else data[name]
+    keys = [by] if hb is None else ([hb.col] if hb.comps is None else hb.comps)
+    # a column that is counted only: its validity is enough
+    values = lambda n: n in keys or lay.entries[spec.entry_names.index(n)].dtype is not None
+    for _, b, data, m, jrow in _host_batches(path, meta, dicts, cl, join, spec.names, batches,
+                                             values):
+        nrows += b.length
+        key = None
+        if battr is not None:
+            key = (np.where(m, battr.codes[jrow] if len(battr.codes) else 0, 0)
+                   .astype(np.int32), None)
+        if by is not None:
+            kv, kok = data[by]
+            kv = np.asarray(kv)
+            if kv.dtype == np.int8 and spec.cols[by].dictionary is None:
+                kv = kv.view(np.uint8)        # 8-bit key: the slot is the byte
+            key = (kv, kok)
+        ecols = [(None, None) if name is None else data[name] for name in spec.entry_names]
+        if spec.keyspec is not None:
+            # the composite path's twin: packed by the same KeySpec
+            kcols, koks = [], []
+            for c in hb.comps:
+                if isinstance(c, JoinAttr):
+                    kcols.append(np.where(m, c.codes[jrow] if len(c.codes) else 0, 0)
+                                 .astype(np.uint32))
+                    koks.append(None)
+                else:
+                    kcols.append(np.asarray(data[c][0]))
+                    koks.append(data[c][1])
+            part, bad = G.host_group_agg_multi(lay.entries, m, spec.keyspec, kcols, koks, ecols)
+            found = G.merge(found, part)
+            misfit[:len(bad)] += bad
+        elif hb is not None:
+            # the hash path's twin: this batch's groups, united by key
+            kv, kok = data[hb.col]
+            found = G.merge(found, G.host_group_agg(lay.entries, m, kv, kok, ecols))
+        else:
+            for e, (v, ok) in enumerate(ecols):
                 A.host_agg(lay, block, e, m, v, ok, key, count_bad=e == 0)
-    finally:
-        src.close()
     if hb is not None:
-        if len(found.keys) > hb.groups:
-            raise RuntimeError(f"GROUP BY HashBy({hb.col!r}): more than groups={hb.groups} "
-                               f"distinct keys: {len(found.keys)} distinct keys seen; scan again "
-                               "with a larger groups=")
+        _check_groups(hb, len(found.keys))
         if spec.keyspec is not None:
             _check_range(spec.keyspec, misfit[:len(spec.keyspec)])
         return _hash_out(spec, found, nrows, {"total_s": time.perf_counter() - t0})

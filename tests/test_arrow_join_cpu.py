@@ -267,6 +267,8 @@ def test_join_refusals(files):
             host_aggregate(path, [], aggs, join=Join(col, dim))
     with pytest.raises(ValueError, match="no column"):
         host_scan_where(path, [], join=Join("nope", dim))
+    with pytest.raises(ValueError, match="no column"):
+        host_scan_where(path, [("nope", 0, 1)])
     with pytest.raises(NotImplementedError, match="one join"):
         host_scan_where(path, [], join=[Join("i64", dim), Join("u32", dim)])
     with pytest.raises(NotImplementedError, match="one join"):

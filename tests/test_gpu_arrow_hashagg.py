@@ -475,6 +475,7 @@ def test_more_groups_than_slots(S, tmp_path):
     from arrowgen import write
     from hashagggen import BIG_AGGS, big_table, check_by_runs
     from nvme_strom_amd.models.arrow_scan import ArrowScan, HashBy
+    from nvme_strom_amd.ops.colpred import P
     tbl = big_table()
     path = str(tmp_path / "big.arrow")
     write(path, tbl, None, batch_rows=4093)
@@ -486,6 +487,20 @@ def test_more_groups_than_slots(S, tmp_path):
         assert g.groups > len(tight._slots) and len(g.keys) == 50_001 and g.keys[-1] is None
         check_by_runs(g, tbl, "k", BIG_AGGS)
         same_results(g, tight.host_aggregate([], BIG_AGGS, by=by))
+        # every kind of query in turn on the one object: they share the slots'
+        # kept tensors, events, counts and key buffer, and the emit stream
+        quals = [P("c") > 0]
+        rows = tight.scan_where(quals, project="a")
+        flat = tight.aggregate(quals, BIG_AGGS)
+        hashed = tight.aggregate(quals, BIG_AGGS, by=by)
+        again = tight.scan_where(quals, project="a")
+        assert rows.groups > len(tight._slots) and 0 < rows.selected < tbl.num_rows
+        ref = tight.host_scan_where(quals, project="a")
+        for out in (rows, again):
+            assert np.array_equal(out.indices.cpu().numpy(), ref.indices)
+            assert np.array_equal(out.values.cpu().numpy(), ref.values)
+        same_results(flat, tight.host_aggregate(quals, BIG_AGGS))
+        same_results(hashed, tight.host_aggregate(quals, BIG_AGGS, by=by))
     finally:
         tight.close()
 

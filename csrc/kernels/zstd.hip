@@ -953,7 +953,14 @@ HD void lit_load(Smem &s, const Ctx &c, uint32_t t) {
 // (1) up to LSYM symbols of literal stream j
 HD void lit_chunk(Smem &s, const Ctx &c, uint32_t j) {
   const uint32_t left = s.lcnt[j];
-  if (!left) return;
+  if (!left) {
+    // done a round before the others (the 4th stream is up to 3 symbols
+    // shorter): nothing staged, or lit_flush would write the last round's
+    // bytes again, past the literals (past the capacity, for a
+    // literals-only block that fills it)
+    s.lrn[j] = 0;
+    return;
+  }
   BR b = s.lbr[j];
   const Win w{(uint32_t)offsetof(Smem, lwin) + j * LWIN, s.lwlo[j], LWIN};
   const uint32_t n = left < LSYM ? left : LSYM, mb = s.hbits;

@@ -178,7 +178,8 @@ def zstd_host(codec: int, data: bytes, cap: int, fp: int = 0, lp: bool = False):
     """The zstd kernel's phases run lane by lane on the CPU
     (csrc/kernels/zstd.hip): -> (status, output bytes).  The reference for
     the GPU decoder; status = decoded bytes or <0 (-1 malformed,
-    -2 overflow, -3 distance, -4 unsupported: a dictionary).  ``fp`` = 2..8
+    -2 overflow, -3 distance, -4 unsupported: a dictionary, -5 content
+    checksum).  ``fp`` = 2..8
     runs the frame-parallel decoder's phases (that many blocks per group,
     waves one after another)."""
     src = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)

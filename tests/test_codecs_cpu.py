@@ -400,10 +400,11 @@ def test_lz4par_fuzz_asan(tmp_path):
 
 
 def test_zstd_fuzz_asan(tmp_path):
-    """8k random edits / truncations of real zstd frames through the
-    decoder's phases built host-only with ASan + UBSan
-    (csrc/tests/zstd_fuzz.cc): seeds decode exactly, mutants end in a
-    clean status, never an out-of-range access."""
+    """2k random edits / truncations each of real zstd frames, and of one
+    hand-built stream per family of tests/zstdgen.py, through the decoder's
+    phases built host-only with ASan + UBSan (csrc/tests/zstd_fuzz.cc):
+    seeds decode exactly, mutants end in a clean status, never an
+    out-of-range access."""
     pa = pytest.importorskip("pyarrow")
     import os
     import subprocess
@@ -419,10 +420,21 @@ def test_zstd_fuzz_asan(tmp_path):
         (tmp_path / f"{i}.zst").write_bytes(z)
         (tmp_path / f"{i}.raw").write_bytes(d)
         args += [str(tmp_path / f"{i}.zst"), str(tmp_path / f"{i}.raw")]
+    import zstdgen as G
+    picks = {"frames": "skip_everywhere", "blocks": "survive_rle", "literals": "litonly_s4_R1025",
+             "sequences": "mode_fse_max_al_lt1_zero_runs", "offsets": "rep_rotation_n391",
+             "fp_carry": "carry_b9_all"}
+    picks = [c for fam, name in picks.items() for c in G.FAMILIES[fam]() if c.name == name] + \
+        [c for c in G.align_streams() if c.name == "align_3blocks"]
+    assert len(picks) == 7
+    for c in picks:
+        (tmp_path / f"{c.name}.zst").write_bytes(c.comp)
+        (tmp_path / f"{c.name}.raw").write_bytes(c.exp)
+        args += [str(tmp_path / f"{c.name}.zst"), str(tmp_path / f"{c.name}.raw")]
     r = subprocess.run([os.path.join(root, "build", "zstd_fuzz"), "2000"] + args,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
-    assert "4 seeds ok" in r.stdout
+    assert "11 seeds ok" in r.stdout
 
 
 def _with_checksum(frame: bytes, data: bytes) -> bytes:

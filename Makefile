@@ -150,6 +150,14 @@ build/lz4par_fuzz: csrc/tests/lz4par_fuzz.cc csrc/kernels/lz4par.hip csrc/includ
 	  -Xarch_host -fno-sanitize-recover=all -fno-omit-frame-pointer \
 	  -o $@ csrc/tests/lz4par_fuzz.cc csrc/kernels/lz4par.hip
 
+# the top-k kernels' host copy (select + merge phases), host-only with ASan + UBSan
+build/coltopk_fuzz: csrc/tests/coltopk_fuzz.cc csrc/kernels/coltopk.hip csrc/include/strom/strom.h
+	@mkdir -p build
+	$(HIPCC) -std=c++17 -O1 -g -Icsrc/include --offload-arch=$(ARCH) \
+	  -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
+	  -Xarch_host -fno-sanitize-recover=all -fno-omit-frame-pointer \
+	  -o $@ csrc/tests/coltopk_fuzz.cc csrc/kernels/coltopk.hip
+
 selftest: build/selftest build/selftest-asan build/selftest-tsan
 	STROM_STAT_SHM=0 ./build/selftest && STROM_STAT_SHM=0 ./build/selftest-asan && STROM_STAT_SHM=0 TSAN_OPTIONS=report_signal_unsafe=0 ./build/selftest-tsan
 

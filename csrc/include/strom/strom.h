@@ -803,6 +803,100 @@ int strom_group_agg_many(const struct strom_agg_entry *e, uint32_t n, const uint
                          uint64_t nwords, const struct strom_filter_batch *d_codes,
                          uint32_t nbatches, uint64_t capacity, int combine, void *stream);
 
+/* ORDER BY one column LIMIT k over the selection bitmap
+ * (csrc/kernels/coltopk.hip; Arrow scans: ArrowScan.top).
+ *
+ * Order: (class, key, row), all ascending.  class 0 a value, 1 a NaN, 2 a
+ * null — in both directions.  key: the MIN / MAX encoding of
+ * strom_column_agg (signed x ^ 2^63, unsigned x, floats as doubles with the
+ * sign bit set for x >= 0 and all bits flipped for x < 0, -0.0 taken as
+ * +0.0), every bit inverted with STROM_TOPK_DESC; 0 for a NaN or a null.
+ * row: the file-global row id (row_base + local row), so the order is total
+ * and equal values come back in file order whatever the direction.
+ *
+ * A candidate is STROM_TOPK_ENTRY_WORDS 64-bit words:
+ *   word 0  key
+ *   word 1  meta = class << 62 | row << 2 | negzero << 1 | pvalid
+ *           (negzero: the value was -0.0; pvalid: the payload is not null;
+ *           rows are < 2^60)
+ *   word 2  payload: the carried column's value of the row, zero-extended
+ *           from pay_width bytes; 0 when it is null or nothing is carried
+ * so a < b is (a.meta >> 62, a.key, a.meta) < (b.meta >> 62, b.key, b.meta).
+ *
+ * State: STROM_TOPK_HDR_WORDS + 3 * k words on the device
+ * (strom_topk_state_words).  Header: K the k it was initialised for, COUNT
+ * the candidates held (<= k), SEEN the selected rows of every group merged
+ * so far, THRESH the threshold key, ERRORS the slabs and states refused (a
+ * count above k, another k: nothing of them is followed), MERGES the merges
+ * done; words 6, 7 are zero.  Then COUNT candidates, sorted; the words behind
+ * them are never written.  THRESH is the key of the k-th candidate once k are
+ * held and that candidate is a value, else ~0 ("everything passes"): a row
+ * may enter the result only if THRESH is ~0 or it is a value with key <=
+ * THRESH.  THRESH only ever decreases.  Only strom_topk_init and
+ * strom_topk_merge write a state.
+ *
+ * strom_column_topk walks the bitmap like strom_column_join (batch b on
+ * words [word_base, ...), the last word bounded by nrows; a null of d_vals is
+ * class 2) with strom_column_topk_grid(nwords, k) workgroups, workgroup g
+ * taking words 4 * g + 4 * grid * t + (0 .. 3), and leaves one slab per
+ * workgroup at d_slabs + g * strom_topk_slab_words(k):
+ *   word 0  n, the candidates that follow (<= k)
+ *   word 1  the selected rows the workgroup walked
+ *   then n candidates, sorted: the workgroup's k best among its rows that
+ *   passed THRESH as it was when the workgroup read it (one 64-bit load; the
+ *   words behind them are not written).
+ * THRESH may be stored by a merge on another stream meanwhile: an older
+ * value passes more rows, never fewer, and every row it rejects is behind k
+ * rows the state already holds.  d_pay (may be NULL): a table of the same
+ * batches for the carried column, pay_width 1, 2, 4 or 8 bytes per row — the
+ * slot's int32 code buffers are such a table.  type: STROM_COL_I8 .. U64,
+ * F32, F64.  The grid keeps grid * k <= 2^18 candidates of slabs.
+ *
+ * strom_topk_merge (one workgroup; the scan runs it in group order on its
+ * emit stream) folds nslabs slabs and the state's candidates into the
+ * state's k best and stores SEEN, COUNT and the new THRESH.
+ *
+ * STROM_TOPK_MAX_K: a workgroup collects candidates in an LDS buffer of C
+ * entries of 24 bytes and sorts it (bitonic, over the entries held: the
+ * network needs no power of two of storage) and cuts it to k whenever more
+ * than C - 256 are held — 256 lanes append between two looks at the fill.
+ * C = max(2k, 64) + 256, at most STROM_TOPK_MAX_K + 256, so C >= k + 256
+ * always.  The CU's LDS is 160 KiB = 163,840 bytes, of which the kernels keep
+ * some 64 bytes besides the buffer: 24 C <= 163,776 allows C = 6,824, k =
+ * 6,568; the limit is the multiple of 1,024 below, a buffer of 150 KiB.
+ *
+ * The strom_topk_host_* functions are the same phases on the CPU over host
+ * pointers, workgroup by workgroup (csrc/tests/coltopk_fuzz.cc runs them
+ * under ASan + UBSan). */
+#define STROM_TOPK_MAX_K 6144
+#define STROM_TOPK_HDR_WORDS 8
+#define STROM_TOPK_ENTRY_WORDS 3
+#define STROM_TOPK_SLAB_HDR_WORDS 2
+#define STROM_TOPK_H_K 0
+#define STROM_TOPK_H_COUNT 1
+#define STROM_TOPK_H_SEEN 2
+#define STROM_TOPK_H_THRESH 3
+#define STROM_TOPK_H_ERRORS 4
+#define STROM_TOPK_H_MERGES 5
+#define STROM_TOPK_DESC 1
+uint64_t strom_topk_state_words(uint32_t k);
+uint64_t strom_topk_slab_words(uint32_t k);
+uint32_t strom_column_topk_grid(uint64_t nwords, uint32_t k);
+int strom_topk_init(uint64_t *d_state, uint32_t k, void *stream);
+int strom_column_topk(int type, uint32_t flags, uint32_t k, const uint64_t *d_bitmap,
+                      uint64_t nwords, const struct strom_filter_batch *d_vals,
+                      const struct strom_filter_batch *d_pay, uint32_t pay_width,
+                      uint32_t nbatches, const uint64_t *d_state, uint64_t *d_slabs,
+                      void *stream);
+int strom_topk_merge(uint32_t k, const uint64_t *d_slabs, uint32_t nslabs, uint64_t *d_state,
+                     void *stream);
+int strom_topk_host_init(uint64_t *state, uint32_t k);
+int strom_topk_host_select(int type, uint32_t flags, uint32_t k, const uint64_t *bitmap,
+                           uint64_t nwords, const struct strom_filter_batch *vals,
+                           const struct strom_filter_batch *pay, uint32_t pay_width,
+                           uint32_t nbatches, const uint64_t *state, uint64_t *slabs);
+int strom_topk_host_merge(uint32_t k, const uint64_t *slabs, uint32_t nslabs, uint64_t *state);
+
 #ifdef __cplusplus
 }
 #endif

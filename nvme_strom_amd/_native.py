@@ -353,6 +353,19 @@ _SIGS = {
                                   C.c_void_p]),
     "strom_group_agg_many": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
                                        C.c_uint32, C.c_uint64, C.c_int, C.c_void_p]),
+    "strom_topk_state_words": (C.c_uint64, [C.c_uint32]),
+    "strom_topk_slab_words": (C.c_uint64, [C.c_uint32]),
+    "strom_column_topk_grid": (C.c_uint32, [C.c_uint64, C.c_uint32]),
+    "strom_topk_init": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "strom_column_topk": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                    C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "strom_topk_merge": (C.c_int, [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "strom_topk_host_init": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "strom_topk_host_select": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                         C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                         C.c_void_p, C.c_void_p]),
+    "strom_topk_host_merge": (C.c_int, [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "strom_io_info": (C.c_int, [C.c_void_p]),
     "strom_io_prof": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "strom_arrow_headers": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,

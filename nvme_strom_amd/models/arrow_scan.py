@@ -43,6 +43,7 @@ from .. import api
 from ..ops import colagg as A
 from ..ops import colgroup as G
 from ..ops import coljoin as J
+from ..ops import coltopk as T
 from ..ops import decompress as D
 from ..ops.colfilter import BATCH_FIELDS, bitmap_to_rows, bitmap_to_rows_str
 from ..ops.colpred import (COL_CODE, QUAL_BATCH_FIELDS, Compiled, Pred, clauses, compile_pred,
@@ -331,6 +332,18 @@ class _HashRun:
 
 
 @dataclass
+class _TopRun:
+    """A scan's ORDER BY ... LIMIT k as _compute sees it."""
+    col: int                      # plan column of the order column
+    code: int                     # its STROM_COL_* storage type
+    descending: bool
+    state: T.State                # the k best so far (device; merged on the emit stream)
+    pcol: Optional[int] = None    # plan column carried with each candidate
+    pwidth: int = 0               # its bytes per row
+    pattr: bool = False           # carry the joined attribute's codes instead
+
+
+@dataclass
 class _Run:
     """One scan as _compute's stages see it: its totals over the groups and
     where its results go.  A stage whose field is None is not called."""
@@ -342,6 +355,7 @@ class _Run:
     marks: list = field(default_factory=list)    # (group, event, clock)
     join: Optional[_JoinRun] = None
     hash: Optional[_HashRun] = None
+    top: Optional[_TopRun] = None
     # rows (scan_where): the row ids and the projection behind their cursors
     out: Optional[torch.Tensor] = None
     cursor: Optional[torch.Tensor] = None
@@ -993,7 +1007,9 @@ class ArrowScan:
             # emit tables: the strom_filter_batch prefix of the qual tables
             any_col = spec[0][0][0] if spec else (run.join.col if run.join is not None else 0)
             d_rows = t.dev5(any_col)
-            args = d_proj = None
+            args = d_proj = slabs = None
+            if run.top is not None:
+                slabs = self._select(s, g, t, run.top, bitmap, d_codes)
             if run.agg is not None:
                 args = self._accumulate(s, g, t, run, any_col, bitmap,
                                         d_codes.data_ptr() if d_codes is not None else 0)
@@ -1002,7 +1018,7 @@ class ArrowScan:
             elif run.pcol is not None:
                 d_proj = t.qual(run.pcol) if run.pchars is not None else t.dev5(run.pcol)
             s.keep += [d_rows] + ([d_proj] if d_proj is not None else [])
-        self._emit(s, g, run, d_rows, d_proj, args)
+        self._emit(s, g, run, d_rows, d_proj, args, slabs)
         run.bytes_read += g.read_bytes
         run.column_bytes += g.column_bytes
         run.marks.append((k, "launched", time.perf_counter()))
@@ -1131,6 +1147,21 @@ class ArrowScan:
                                 stream=s.stream)
         return s.bitmap, d_h[-1]
 
+    def _select(self, s: _Slot, g: _Group, t: _Tables, tr: _TopRun, bitmap: torch.Tensor,
+                d_codes: Optional[torch.Tensor]) -> tuple:
+        """ORDER BY ... LIMIT k: the group's candidates over the selection the
+        qualifiers and the probe left (csrc/kernels/coltopk.hip), each
+        workgroup's k best in a slab.  The launch reads the state's threshold
+        as the emit stream's merges have left it so far.  Returns (slabs, how
+        many) for the emit stream to merge."""
+        both = [t.host5(tr.col)] + ([t.host5(tr.pcol)] if tr.pcol is not None else [])
+        d_t = self._upload(s, np.stack(both))
+        d_pay = d_codes if tr.pattr else (d_t[1] if tr.pcol is not None else None)
+        slabs, n = T.select(tr.state, tr.code, d_t[0], g.words, bitmap, tr.descending,
+                            pay=d_pay, pay_width=tr.pwidth, stream=s.stream)
+        s.keep += [d_t, slabs]
+        return slabs, n
+
     def _accumulate(self, s: _Slot, g: _Group, t: _Tables, run: _Run, any_col: int,
                     bitmap: torch.Tensor, key_ptr: int):
         """The aggregate launches over the selection.  The host's time here
@@ -1171,7 +1202,7 @@ class ArrowScan:
         return args
 
     def _emit(self, s: _Slot, g: _Group, run: _Run, d_rows: torch.Tensor,
-              d_proj: Optional[torch.Tensor], args) -> None:
+              d_proj: Optional[torch.Tensor], args, slabs=None) -> None:
         """Decode + filter of successive groups overlap on their slots'
         streams; the row-id emit (+ projection gather) and the fold of the
         slabs run in group order on one stream (the output cursor and the
@@ -1184,6 +1215,10 @@ class ArrowScan:
             if args is not None:
                 # the slabs into the scan's accumulator block, in group order
                 A.agg_reduce_many(run.agg.layout, args, g.words, stream=es)
+            if slabs is not None:
+                # the group's candidates into the scan's k best, in group order;
+                # the new threshold is there for the launches not yet queued
+                T.merge(run.top.state, slabs[0], slabs[1], stream=es)
             if run.pchars is not None:
                 bitmap_to_rows_str(s.bitmap, g.words, d_rows, run.out, run.cursor, d_proj,
                                    run.owidth, run.poff, run.pchars, run.ccursor,
@@ -1486,6 +1521,84 @@ class ArrowScan:
         aggregate kernels' numpy twin, ops/colagg.py)."""
         return host_aggregate(self.path, quals, aggs, by, batches, meta=self.meta,
                               dicts=self._dicts, join=join)
+
+    def top(self, quals, order_by: str, k: int, descending: bool = False, project=None,
+            batches: Optional[Tuple[int, int]] = None, join: Optional[Join] = None) -> "TopOut":
+        """``SELECT row, order_by[, project] WHERE quals ORDER BY order_by
+        [DESC] LIMIT k`` in one pass: the first ``k`` of the selected rows by
+        (a value before a NaN before a null — in both directions —, the value
+        ascending or descending, the file-global row id ascending), which is
+        ``pyarrow.compute.sort_indices`` with its default null placement,
+        cut to ``k``.  -0.0 and +0.0 are equal; integers compare by value,
+        uint64 over its whole range, temporal columns by their ticks.
+
+        Per group a selection kernel (csrc/kernels/coltopk.hip) on the slot's
+        stream leaves each workgroup's ``k`` best candidates, a merge on the
+        emit stream folds them into the scan's state of ``k`` candidates and
+        tightens the threshold the later groups' launches read; the state's
+        few KB are read back at the scan's one sync.  No row ids are written
+        and nothing of the table's height is allocated.
+
+        ``order_by``: a non-dictionary int8-64, uint8-64, float32/64, date,
+        time, timestamp or duration column.  ``k``: 1 .. ops.coltopk.MAX_K;
+        more than the selected rows returns them all, sorted.  ``project``:
+        one column carried with each candidate — fixed-width of at most 8
+        bytes, a dictionary-encoded column's indices (``TopOut.dictionary``
+        holds the values) or ``dim[attr]`` of the semi-join.  ``quals`` (may
+        be empty), ``batches`` and ``join`` as in scan_where.  One order
+        column, no OFFSET.  See TopOut."""
+        t0 = time.perf_counter()
+        k = T.check_k(k)
+        pattr = project if isinstance(project, JoinAttr) else None
+        join = _check_join(self.meta, join, pattr)
+        if pattr is not None:
+            project = None
+        spec_out = _top_spec(self.meta, order_by, k, descending, project, pattr, self.dictionary)
+        cl = clauses(quals) if quals else []
+        names = _scanned(cl, join, [order_by] + ([project] if project else []))
+        cols, nrows, groups = self._resolve(names, batches)
+        spec = [[(names.index(p.col), self._compile(p)) for p in c] for c in cl]
+        t_plan = time.perf_counter()
+        none = np.zeros((0, T.ENTRY_WORDS), np.uint64)
+        if not groups or nrows == 0:
+            return _top_out(spec_out, none, nrows, 0, {"total_s": time.perf_counter() - t0})
+        # the state is initialised on the emit stream, where the merges follow
+        es = self._emit_stream()
+        with torch.cuda.stream(es):
+            state = T.init(k, self.device, stream=es)
+        run = _Run(self._zero(), self._zero())
+        run.top = _TopRun(names.index(order_by), T.TYPE_CODE[spec_out.column.storage],
+                          bool(descending), state,
+                          names.index(project) if project else None,
+                          4 if pattr is not None else
+                          (np.dtype(spec_out.pcolumn.storage).itemsize if project else 0),
+                          pattr is not None)
+        if join is not None:
+            run.join = self._join_run(join, names, pattr)
+        # the select launches (slot streams) read the state's threshold: they
+        # must see it initialised
+        run.block_ready = torch.cuda.Event()
+        run.block_ready.record(es)
+        t_alloc = self._drive(groups, spec, run)
+        host = torch.cat([state.words, run.err]).cpu().numpy()
+        secs = self._seconds(run, t0, t_plan, t_alloc)
+        self._check_decoded(int(host[-1]), names)
+        words = host[:-1].view(np.uint64)
+        if int(words[T.H_ERRORS]) or int(words[T.H_MERGES]) != len(groups):
+            raise RuntimeError(f"top-k state: {int(words[T.H_ERRORS])} slab(s) refused, "
+                               f"{int(words[T.H_MERGES])} merges for {len(groups)} groups")
+        secs["timeline_ms"] = [(i, e, round((t - t_alloc) * 1e3, 3)) for i, e, t in run.marks]
+        return _top_out(spec_out, T.state_entries(words).copy(), nrows, int(words[T.H_SEEN]), secs,
+                        bytes_read=run.bytes_read, column_bytes=run.column_bytes,
+                        groups=len(groups))
+
+    def host_top(self, quals, order_by: str, k: int, descending: bool = False, project=None,
+                 batches: Optional[Tuple[int, int]] = None,
+                 join: Optional[Join] = None) -> "TopOut":
+        """The same query on the CPU (the host twins' scan, the candidates'
+        numpy twin, ops/coltopk.py)."""
+        return host_top(self.path, quals, order_by, k, descending, project, batches,
+                        meta=self.meta, dicts=self._dicts, join=join)
 
     def scan(self, name: str, lo, hi) -> ScanOut:
         """Row ids (int64, file order) of ``lo <= column <= hi`` (nulls never
@@ -2072,3 +2185,159 @@ def host_aggregate(path: str, quals, aggs, by=None,
             _check_range(spec.keyspec, misfit[:len(spec.keyspec)])
         return _hash_out(spec, found, nrows, {"total_s": time.perf_counter() - t0})
     return _agg_out(spec, block, nrows, {"total_s": time.perf_counter() - t0})
+
+
+# ------------------------------------------------------------ ORDER BY ... LIMIT k
+@dataclass
+class _TopSpec:
+    order_by: str
+    k: int
+    descending: bool
+    column: Column                          # the order column
+    nullable: bool                          # ... has nulls somewhere in the file
+    project: Optional[str] = None           # the carried column's (or attribute's) name
+    pcolumn: Optional[Column] = None
+    pnullable: bool = False
+    pattr: bool = False
+    dictionary: object = None
+
+    def same(self, o: "_TopSpec") -> bool:
+        return (self.order_by, self.k, self.descending, self.project, self.pattr) == \
+            (o.order_by, o.k, o.descending, o.project, o.pattr) and \
+            (not self.pattr or self.dictionary == o.dictionary)
+
+
+def _file_nulls(meta: ArrowFile, name: str) -> bool:
+    """Whether any record batch of the file has nulls in the column — the
+    whole file, whatever range is scanned, so that results of ranges merge."""
+    ci = meta.column_index(name)
+    return bool(meta.nbatches) and bool(np.any(np.asarray(meta.columns[ci].null_count)))
+
+
+def _top_spec(meta: ArrowFile, order_by: str, k: int, descending: bool, project: Optional[str],
+              pattr: Optional[JoinAttr], dictionary) -> _TopSpec:
+    """Validate the order and carried columns of ``top`` against the schema."""
+    schema = {c.name: c for c in meta.schema}
+    if not isinstance(order_by, str):
+        raise NotImplementedError("ORDER BY one column (a list of order columns is not supported)")
+    if order_by not in schema:
+        raise ValueError(f"no column {order_by!r}")
+    c = schema[order_by]
+    if c.dictionary is not None or c.kind not in ("int", "float") + _TEMPORAL or \
+            c.storage not in T.TYPE_CODE:
+        kind = "dictionary-encoded" if c.dictionary is not None else c.kind
+        raise NotImplementedError(f"ORDER BY {order_by}: {kind} columns are not ordered on the "
+                                  "GPU (integer, float32/64, date, time, timestamp and duration "
+                                  "columns are)")
+    out = _TopSpec(order_by, k, bool(descending), c, _file_nulls(meta, order_by))
+    if pattr is not None:
+        out.project, out.pattr, out.dictionary = pattr.name, True, pattr.values
+    elif project is not None:
+        if project not in schema:
+            raise ValueError(f"no column {project!r}")
+        p = schema[project]
+        if p.dictionary is None and (p.kind in ("utf8", "binary", "decimal", "bool") or
+                                     p.storage not in _TORCH):
+            raise NotImplementedError(f"top: projection of {project} ({p.kind}): one fixed-width "
+                                      "column of at most 8 bytes or a dictionary-encoded "
+                                      "column's indices is carried; the row ids serve the rest")
+        out.project, out.pcolumn, out.pnullable = project, p, _file_nulls(meta, project)
+        if p.dictionary is not None:
+            out.dictionary = dictionary(project)
+    return out
+
+
+@dataclass
+class TopOut:
+    """Result of ArrowScan.top / host_top (host side, numpy), in result
+    order: ``rows`` the int64 file-global row ids, ``values`` the order
+    column in its storage dtype (ticks for temporal columns: ``column`` holds
+    the type; NaN for a NaN of any payload, 0 for a null), ``valid`` its
+    validity when the file has nulls in that column, else None.
+    ``projected`` / ``projected_valid``: the carried column (indices for a
+    dictionary-encoded one, codes for ``dim[attr]``: ``dictionary`` holds
+    their values; 0 for a null) and its validity when the file has nulls in
+    it.  ``nrows``: the rows scanned, ``selected``: the rows the qualifiers
+    and the join selected."""
+    rows: np.ndarray
+    values: np.ndarray
+    valid: Optional[np.ndarray]
+    projected: Optional[np.ndarray]
+    projected_valid: Optional[np.ndarray]
+    nrows: int
+    selected: int
+    seconds: Dict[str, float]
+    bytes_read: int = 0
+    column_bytes: int = 0
+    groups: int = 0
+    column: Optional[Column] = None
+    dictionary: object = None
+    _spec: Optional[_TopSpec] = None
+    _entries: Optional[np.ndarray] = None   # the candidates (ops/coltopk.py)
+
+    def merge(self, other: "TopOut") -> "TopOut":
+        """The ``k`` best of this result and another of the same query over
+        other record batches of the same file (another rank), on the host."""
+        a, b = self._spec, other._spec
+        if not a.same(b):
+            raise ValueError("merge: results of another order column, direction, k or carried "
+                             "column")
+        secs = {"total_s": self.seconds.get("total_s", 0.0) + other.seconds.get("total_s", 0.0)}
+        ent = T.best(np.concatenate([self._entries, other._entries]), a.k)
+        return _top_out(a, ent, self.nrows + other.nrows, self.selected + other.selected, secs,
+                        bytes_read=self.bytes_read + other.bytes_read,
+                        column_bytes=self.column_bytes + other.column_bytes,
+                        groups=self.groups + other.groups)
+
+
+def _top_out(spec: _TopSpec, ent: np.ndarray, nrows: int, selected: int,
+             seconds: Dict[str, float], **kw) -> TopOut:
+    rows, vals, ok, pay, pok = T.decode(ent, spec.column.storage, spec.descending)
+    proj = pvalid = None
+    if spec.pattr:
+        proj = T.payload_as(pay, np.int32)
+    elif spec.project is not None:
+        proj = T.payload_as(pay, spec.pcolumn.storage)
+        pvalid = pok if spec.pnullable else None
+    return TopOut(rows, vals, ok if spec.nullable else None, proj, pvalid, nrows, selected,
+                  seconds, column=spec.column, dictionary=spec.dictionary, _spec=spec,
+                  _entries=ent, **kw)
+
+
+def host_top(path: str, quals, order_by: str, k: int, descending: bool = False, project=None,
+             batches: Optional[Tuple[int, int]] = None, meta: Optional[ArrowFile] = None,
+             dicts: Optional[dict] = None, join: Optional[Join] = None) -> TopOut:
+    """ArrowScan.top on the CPU: the host twins' scan, then numpy ``lexsort``
+    on (class, key, row) of the candidates (ops/coltopk.py), batch by batch.
+    The reference point for the GPU path and the same answer without one."""
+    t0 = time.perf_counter()
+    meta = meta if meta is not None else read_metadata(path)
+    dicts = dicts if dicts is not None else {}
+    k = T.check_k(k)
+    pattr = project if isinstance(project, JoinAttr) else None
+    join = _check_join(meta, join, pattr)
+    if pattr is not None:
+        project = None
+    spec = _top_spec(meta, order_by, k, descending, project, pattr,
+                     lambda name: _dictionary(meta, path, dicts, name))
+    cl = clauses(quals) if quals else []
+    base = np.concatenate([[0], np.cumsum(meta.rows)]).astype(np.int64)
+    ent = np.zeros((0, T.ENTRY_WORDS), np.uint64)
+    nrows = selected = 0
+    for bi, b, data, m, jrow in _host_batches(path, meta, dicts, cl, join,
+                                              [order_by] + ([project] if project else []),
+                                              batches):
+        nrows += b.length
+        sel = np.flatnonzero(m)
+        selected += len(sel)
+        v, ok = data[order_by]
+        pay = pok = None
+        if pattr is not None:
+            pay = pattr.codes[jrow[sel]] if len(pattr.codes) else np.zeros(0, np.int32)
+        elif project:
+            pv, pk = data[project]
+            pay, pok = np.asarray(pv)[sel], (None if pk is None else pk[sel])
+        e = T.entries(np.asarray(v)[sel], None if ok is None else ok[sel], sel + base[bi],
+                      spec.descending, pay, pok)
+        ent = T.best(np.concatenate([ent, e]), k)
+    return _top_out(spec, ent, nrows, selected, {"total_s": time.perf_counter() - t0})

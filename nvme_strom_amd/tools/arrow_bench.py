@@ -471,6 +471,78 @@ def hashagg_row(path: str, fd: int, a, col) -> dict:
     return row
 
 
+def topk_rows(path: str, fd: int, a, col) -> dict:
+    """ORDER BY ... LIMIT k rows: ``top val k=100`` (the ``val`` row's range
+    as qualifier, ORDER BY val LIMIT 100), the same under qual2's two-column
+    qualifier list with ``id`` carried, and ``x`` descending under the ``x``
+    row's range (5 % nulls).  Each is alternated A B A B ... (--topk-pairs
+    pairs, the file evicted before every scan) with A = ``scan_where`` of the
+    same qualifier list and projection, which reads the same columns — what a
+    caller had to run before, without the torch.topk it then still needed —
+    and verified against numpy on the host (lexsort on class, key, row over
+    the selected rows)."""
+    import torch
+
+    import nvme_strom_amd as S
+    from nvme_strom_amd.models.arrow_scan import ArrowScan
+    from nvme_strom_amd.ops import coltopk as T
+    val_q = [("val", 100_000, 199_999)]
+    specs = [("top val k=100", val_q, "val", 100, False, None),
+             ("top val k=100 qual2", [("val", 100_000, 599_999), ("x", 0.25, 0.75)], "val", 100,
+              False, "id"),
+             ("top x desc k=100", [("x", 0.25, 0.5)], "x", 100, True, None)]
+    rows = {}
+    for label, quals, order, k, desc, proj in specs:
+        sc = ArrowScan(path, "cuda", slot_bytes=a.slot_mib << 20, nslots=a.nslots or None,
+                       chunk_sz=(a.chunk_kib << 10) or None)
+        try:
+            def timed(fn):
+                S.evict_file(fd)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                out = fn()
+                return time.perf_counter() - t1, out
+            scan = lambda: sc.scan_where(quals, project=proj)
+            top = lambda: sc.top(quals, order, k, desc, project=proj)
+            timed(scan), timed(top)                       # plans, slots, code objects
+            ta, tb = [], []
+            for _ in range(a.topk_pairs):
+                dt, base = timed(scan)
+                ta.append(dt)
+                dt, out = timed(top)
+                tb.append(dt)
+        finally:
+            sc.close()
+        m = None
+        for name, lo, hi in quals:
+            vals, valid = col(name)
+            mm = (vals >= lo) & (vals <= hi)
+            if valid is not None:
+                mm &= valid
+            m = mm if m is None else m & mm
+        ids = np.flatnonzero(m)
+        ov, ovalid = col(order)
+        want = T.best(T.entries(ov[ids], None if ovalid is None else ovalid[ids], ids, desc,
+                                ids.astype(np.int64) if proj else None), k)   # id is the row id
+        ok = bool(np.array_equal(out._entries, want) and out.selected == len(ids) and
+                  base.selected == len(ids))
+        ma, mb = float(np.median(ta)), float(np.median(tb))
+        rows[label] = dict(
+            quals=[repr(q) for q in quals], order_by=order, k=k, descending=desc, project=proj,
+            verified=ok,
+            selected=out.selected, groups=out.groups, column_bytes=out.column_bytes,
+            bytes_read=out.bytes_read, scan_where_bytes_read=base.bytes_read,
+            scan_where_ms=[round(x * 1e3, 2) for x in ta], top_ms=[round(x * 1e3, 2) for x in tb],
+            scan_where_median_ms=round(ma * 1e3, 2), top_median_ms=round(mb * 1e3, 2),
+            scan_where_spread_ms=round((max(ta) - min(ta)) * 1e3, 2),
+            top_minus_scan_where_ms=round((mb - ma) * 1e3, 2),
+            column_GBps=round(out.column_bytes / mb / 1e9, 2),
+            last_breakdown_s={k_: (round(v, 4) if isinstance(v, float) else v)
+                              for k_, v in out.seconds.items() if k_ != "timeline_ms"})
+        _log(label, json.dumps(rows[label]))
+    return rows
+
+
 def make_pairs_file(path: str, rows: int, batch_rows: int, side: int = 1024, seed: int = 9,
                     codec: str = "lz4") -> None:
     """``id`` int64 (the row number), ``a`` and ``b`` int32 uniform over
@@ -592,6 +664,10 @@ def main(argv=None) -> int:
                          "with the same aggregates without a key (--agg-pairs pairs), and "
                          "the row GROUP BY HashBy([a, b]), a million pairs of two int32 "
                          "columns, alternated with HashBy of the pairs as one int64 column")
+    ap.add_argument("--topk", action="store_true",
+                    help="add the ORDER BY ... LIMIT k rows: ArrowScan.top alternated with "
+                         "scan_where of the same qualifier list (--topk-pairs pairs)")
+    ap.add_argument("--topk-pairs", type=int, default=4)
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     import torch
@@ -704,6 +780,8 @@ def main(argv=None) -> int:
             res["join"] = join_rows(path, fd, a, col)
         if a.hashagg:
             res["hashagg"] = hashagg_row(path, fd, a, col)
+        if a.topk:
+            res["topk"] = topk_rows(path, fd, a, col)
     finally:
         os.close(fd)
     if a.hashagg:
@@ -758,6 +836,7 @@ def main(argv=None) -> int:
     res["verified"] = all(c["verified"] for c in res["columns"].values()) and \
         all(r["verified"] for r in res.get("agg", {}).values()) and \
         all(r["verified"] for r in res.get("join", {}).values()) and \
+        all(r["verified"] for r in res.get("topk", {}).values()) and \
         res.get("hashagg", {}).get("verified", True) and \
         res.get("hashagg2", {}).get("verified", True)
     js = json.dumps(res)

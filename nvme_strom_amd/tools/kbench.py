@@ -37,7 +37,8 @@ def main(argv=None):
                     help="also: mvcc (snapshot check), par (LZ4 decoders by stream count), "
                          "agg (aggregate kernels next to column_filter_i64), "
                          "join (hash-join probe next to column_filter_i64), "
-                         "hashagg (hash GROUP BY next to column_filter_i64 and the LDS path)")
+                         "hashagg (hash GROUP BY next to column_filter_i64 and the LDS path), "
+                         "topk (ORDER BY ... LIMIT k select + merge next to column_filter_i64)")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     only = set(a.only.split(","))
@@ -187,6 +188,8 @@ def main(argv=None):
         _join_rows(n, dev, log, column_filter)
     if "hashagg" in only:
         _hashagg_rows(n, dev, log, column_filter)
+    if "topk" in only:
+        _topk_rows(n, dev, log, column_filter)
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:
@@ -275,6 +278,54 @@ def _join_rows(n, dev, log, column_filter):
         print(f"column_join table {tag}: {nk} keys, largest displacement {int(hdr[J.H_MAXDISP])}",
               file=sys.stderr, flush=True)
         del fk, table
+
+
+def _topk_rows(n, dev, log, column_filter):
+    """ORDER BY ... LIMIT k (coltopk.hip: the select launch over the column
+    plus the merge of its slabs into a state that starts empty, so no
+    threshold from an earlier group helps) on one HBM-resident record batch,
+    ascending: GB/s of the column bytes, next to column_filter_i64 of the same
+    run.  int64 and float64 keys, uniform, sorted ascending (the first rows
+    win: the workgroups' own thresholds prune the rest) and sorted descending
+    (every row beats what its workgroup holds: it sorts and cuts at every
+    trip), k = 10, 100 and 1,024, every row selected and 1 %.  Each row's
+    result is checked against torch.topk of the keys."""
+    from nvme_strom_amd.ops import coltopk as T
+    nv = n // 8
+    nwords = (nv + 63) // 64
+    v = torch.randint(-1000, 1000, (nv,), dtype=torch.int64, device=dev)
+    log("column_filter_i64", timed(lambda: column_filter(v, -100, 100), 20), nv * 8)
+    sels = {"100": torch.full((nwords,), -1, dtype=torch.int64, device=dev),
+            "1": column_filter(v, -10, 9)[0]}
+    del v
+    picked = {sel: torch.from_numpy(np.unpackbits(bm.cpu().numpy().view(np.uint8),
+                                                  bitorder="little")[:nv].astype(bool)).to(dev)
+              for sel, bm in sels.items()}
+    for st, make in (("i8", lambda: torch.randint(-2**62, 2**62, (nv,), dtype=torch.int64,
+                                                  device=dev)),
+                     ("f8", lambda: torch.rand(nv, dtype=torch.float64, device=dev))):
+        for shape in ("uniform", "asc", "desc"):
+            col = make()
+            if shape != "uniform":
+                col = torch.sort(col, descending=shape == "desc")[0]
+            tab = torch.tensor([[col.data_ptr(), 0, nv, 0, 0]], dtype=torch.int64, device=dev)
+            for k in (10, 100, 1024):
+                slabs = torch.empty(T.grid(nwords, k) * T.slab_words(k), dtype=torch.int64,
+                                    device=dev)
+                for sel, bm in sels.items():
+                    state = T.init(k, dev)
+
+                    def go():
+                        T.init(k, dev, words=state.words)
+                        _, g = T.select(state, T.TYPE_CODE[st], tab, nwords, bm, slabs=slabs)
+                        T.merge(state, slabs, g)
+                    log(f"column_topk_{st}_{shape}_k{k}_sel{sel}", timed(go, 10), nv * 8)
+                    # verify: the k smallest selected keys
+                    rows, vals, _, _, _ = T.decode(T.state_entries(state.to_host()), st)
+                    want = torch.topk(col[picked[sel]], k, largest=False, sorted=True)[0]
+                    assert np.array_equal(vals, want.cpu().numpy()), (st, shape, k, sel)
+                    assert np.array_equal(col[torch.from_numpy(rows).to(dev)].cpu().numpy(), vals)
+            del col, tab
 
 
 def _hashagg_rows(n, dev, log, column_filter):

@@ -711,6 +711,44 @@ int strom_column_join(int type, int how, const uint64_t *d_table, uint64_t capac
                       const uint64_t *d_src, uint64_t *d_dst,
                       const struct strom_filter_batch *d_kout, uint64_t *d_count, void *stream);
 
+/* A star join: 1 .. STROM_JOIN_MAX_LEGS tables applied in one walk of the
+ * bitmap, in the order given (the caller puts the most selective leg first; a
+ * row an earlier leg has dropped issues no load for the later ones).
+ *   d_dst[w] = the rows of d_src[w] that exist and pass every leg
+ * where a SEMI leg passes a row whose fk is not null and is a key of its table
+ * and an ANTI leg a row whose fk is null or is not.  d_dst may be d_src (a word
+ * that stays as it is is not stored); *d_count += popcount of the d_dst words.
+ * Leg i reads the fk column whose batch table is d_fk[i * nbatches ..]; every
+ * leg's table describes the same batches.  Per leg: `table` / `capacity` as
+ * for strom_column_join, `type` the fk's storage (the eight integer types),
+ * `how` SEMI or ANTI, `kout` -1 or the index of the leg's code table in d_kout
+ * (table j: d_kout[j * nbatches ..], values pointing to int32 buffers of nrows
+ * elements): SEMI legs only, every index below STROM_JOIN_MAX_LEGS and used by
+ * one leg at most.  The leg's payload is stored for exactly the rows of the
+ * d_dst word; no other element of a code buffer is touched.  -EINVAL for a
+ * misaligned or NULL table, a capacity that is no power of two >= 64, another
+ * type or how, kout on an ANTI leg or without d_kout, nlegs 0 or above the
+ * maximum. */
+#define STROM_JOIN_MAX_LEGS 4
+struct strom_join_leg {
+	const uint64_t *table;
+	uint64_t capacity;
+	uint32_t type;
+	uint32_t how;
+	int32_t kout;
+	uint32_t reserved;
+};
+struct strom_join_legs {
+	uint32_t nlegs;
+	uint32_t reserved;
+	struct strom_join_leg leg[STROM_JOIN_MAX_LEGS];
+};
+int strom_column_join_star(struct strom_join_legs legs,
+                           const struct strom_filter_batch *d_fk, uint32_t nbatches,
+                           uint64_t nwords, const uint64_t *d_src, uint64_t *d_dst,
+                           const struct strom_filter_batch *d_kout, uint64_t *d_count,
+                           void *stream);
+
 /* Hash GROUP BY on an integer key column (csrc/kernels/colgroup.hip; Arrow
  * scans: by=HashBy(col) of ArrowScan.aggregate) for key domains that do not
  * fit strom_column_agg's LDS.

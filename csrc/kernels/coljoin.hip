@@ -254,7 +254,163 @@ int launch_probe(const uint64_t *table, uint64_t capacity, const strom_filter_ba
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
+// ------------------------------------------------------------- star probe
+// Several dimension tables in one walk of the bitmap (a star join): leg after
+// leg narrows the word, a row a leg has dropped issues no load for the legs
+// behind it, and each semi leg's payload waits in a register until the last
+// leg has decided the word.  The legs are a template parameter (every loop
+// over them unrolls, their constants stay scalar); the storage type of a
+// leg's fk column is a run-time switch around the one load.
+__device__ __forceinline__ bool load_fk(uint32_t type, const void *p, uint64_t i, uint64_t &key) {
+  switch (type) {
+    case STROM_COL_I8: key = (uint64_t)(int64_t)((const int8_t *)p)[i]; return true;
+    case STROM_COL_I16: key = (uint64_t)(int64_t)((const int16_t *)p)[i]; return true;
+    case STROM_COL_I32: key = (uint64_t)(int64_t)((const int32_t *)p)[i]; return true;
+    case STROM_COL_U8: key = ((const uint8_t *)p)[i]; return true;
+    case STROM_COL_U16: key = ((const uint16_t *)p)[i]; return true;
+    case STROM_COL_U32: key = ((const uint32_t *)p)[i]; return true;
+    case STROM_COL_I64: key = ((const uint64_t *)p)[i]; return true;
+    default: key = ((const uint64_t *)p)[i]; return key <= (uint64_t)INT64_MAX;   // U64
+  }
+}
+
+template <int NL>
+__global__ __launch_bounds__(256) void join_star_kernel(strom_join_legs legs,
+                                                        const strom_filter_batch *__restrict__ ft,
+                                                        uint32_t nb, uint64_t nwords,
+                                                        const uint64_t *src, uint64_t *dst,
+                                                        const strom_filter_batch *__restrict__ kt,
+                                                        ull *__restrict__ count) {
+  __shared__ uint32_t wave_cnt[4];
+  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  uint32_t local = 0;
+  const uint64_t step = (uint64_t)gridDim.x * 4 * kU;
+  for (uint64_t w0 = ((uint64_t)blockIdx.x * 4 + wid) * kU; w0 < nwords; w0 += step) {
+    uint64_t raw[kU], cur[kU], bk[kU];   // the source word, the rows still in, the batch's word
+    uint32_t bi[kU];
+    uint32_t pay[NL][kU];
+#pragma unroll
+    for (uint32_t u = 0; u < kU; ++u) {
+      const uint64_t w = w0 + u;
+      raw[u] = 0;
+      cur[u] = 0;
+      bk[u] = 0;
+      bi[u] = 0;
+      if (w >= nwords) continue;
+      const uint64_t word = src[w];                    // uniform load, one per wave
+      if (!word) continue;
+      raw[u] = word;
+      bi[u] = batch_of(ft, nb, w);                     // every leg's table has the same batches
+      const strom_filter_batch &b = ft[bi[u]];
+      bk[u] = w - b.word_base;
+      cur[u] = word & row_mask(b, bk[u]);
+    }
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+      const strom_join_leg lg = legs.leg[l];
+      const uint64_t mask = lg.capacity - 1;
+      const ulonglong2 *slots = (const ulonglong2 *)(lg.table + kHdr);
+      uint64_t maxd = lg.table[STROM_JOIN_H_MAXDISP];
+      if (maxd > mask) maxd = mask;
+      uint64_t key[kU], at[kU];
+      bool act[kU], hit[kU];
+      ulonglong2 e[kU];
+      // pass 1: the fk of the rows still in, the home slot's load
+#pragma unroll
+      for (uint32_t u = 0; u < kU; ++u) {
+        key[u] = 0;
+        at[u] = 0;
+        act[u] = false;
+        hit[u] = false;
+        pay[l][u] = 0;
+        e[u] = make_ulonglong2(kEmpty, 0);
+        if (!cur[u]) continue;
+        const strom_filter_batch &b = ft[(uint64_t)l * nb + bi[u]];
+        uint64_t use = cur[u];
+        if (b.valid) use &= ((const uint64_t *)b.valid)[bk[u]];
+        if (!((use >> lane) & 1)) continue;
+        if (!load_fk(lg.type, (const void *)b.values, bk[u] * 64 + lane, key[u])) continue;
+        if (key[u] == kEmpty) {
+          hit[u] = lg.table[STROM_JOIN_H_HAS_EMPTY] != 0;
+          pay[l][u] = (uint32_t)lg.table[STROM_JOIN_H_EMPTY_PAYLOAD];
+          continue;
+        }
+        act[u] = true;
+        at[u] = fmix64(key[u]) & mask;
+        e[u] = slots[at[u]];
+      }
+      // pass 2: compare, and walk on while the slot holds another key
+#pragma unroll
+      for (uint32_t u = 0; u < kU; ++u) {
+        if (!cur[u]) continue;
+        bool go = act[u];
+        for (uint64_t d = 0;; ++d) {
+          if (go) {
+            if (e[u].x == key[u]) {
+              hit[u] = true;
+              pay[l][u] = (uint32_t)e[u].y;
+              go = false;
+            } else if (e[u].x == kEmpty || d >= maxd) {
+              go = false;
+            }
+          }
+          if (!__ballot(go)) break;
+          if (go) {
+            at[u] = (at[u] + 1) & mask;
+            e[u] = slots[at[u]];
+          }
+        }
+        const uint64_t match = __ballot(hit[u]);
+        cur[u] = lg.how == STROM_JOIN_ANTI ? cur[u] & ~match : cur[u] & match;
+      }
+    }
+    // the word is decided: the payloads of its rows, the word, the count
+#pragma unroll
+    for (uint32_t u = 0; u < kU; ++u) {
+      const uint64_t w = w0 + u;
+      if (w >= nwords) break;
+      if ((cur[u] >> lane) & 1) {
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+          const int32_t ko = legs.leg[l].kout;
+          if (ko >= 0)
+            ((int32_t *)kt[(uint64_t)ko * nb + bi[u]].values)[bk[u] * 64 + lane] =
+                (int32_t)pay[l][u];
+        }
+      }
+      // in place, a word that stays as it is (a zero one above all) is not stored
+      if (lane == 0 && (dst != src || cur[u] != raw[u])) dst[w] = cur[u];
+      local += __popcll(cur[u]);
+    }
+  }
+  if (lane == 0) wave_cnt[wid] = local;
+  __syncthreads();
+  if (threadIdx.x == 0 && count)
+    atomicAdd(count, (ull)(wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3]));
+}
+
+template <int NL>
+int launch_star(const strom_join_legs &legs, const strom_filter_batch *ft, uint32_t nb,
+                uint64_t nwords, const uint64_t *src, uint64_t *dst, const strom_filter_batch *kt,
+                uint64_t *count, hipStream_t st) {
+  const uint64_t g = (nwords + 4 * kU - 1) / (4 * kU);
+  const uint32_t grid = (uint32_t)(g > kMaxGrid ? kMaxGrid : (g ? g : 1));
+  hipLaunchKernelGGL(join_star_kernel<NL>, dim3(grid), dim3(256), 0, st, legs, ft, nb, nwords, src,
+                     dst, kt, (ull *)count);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
 bool pow2(uint64_t x) { return x && !(x & (x - 1)); }
+
+bool fk_type(uint32_t t) {
+  switch (t) {
+    case STROM_COL_I8: case STROM_COL_I16: case STROM_COL_I32: case STROM_COL_I64:
+    case STROM_COL_U8: case STROM_COL_U16: case STROM_COL_U32: case STROM_COL_U64:
+      return true;
+    default:
+      return false;       // floats, strings, bool, decimal: no integer key
+  }
+}
 
 }  // namespace
 
@@ -309,4 +465,35 @@ extern "C" int strom_column_join(int type, int how, const uint64_t *d_table, uin
     default: return -22;        // floats, strings, bool, decimal: no integer key
   }
 #undef JOIN
+}
+
+extern "C" int strom_column_join_star(struct strom_join_legs legs,
+                                      const strom_filter_batch *d_fk, uint32_t nbatches,
+                                      uint64_t nwords, const uint64_t *d_src, uint64_t *d_dst,
+                                      const strom_filter_batch *d_kout, uint64_t *d_count,
+                                      void *stream) {
+  if (!legs.nlegs || legs.nlegs > STROM_JOIN_MAX_LEGS) return -22;
+  uint32_t outs = 0;                                  // the code tables taken so far
+  for (uint32_t l = 0; l < legs.nlegs; ++l) {
+    const strom_join_leg &g = legs.leg[l];
+    if (!g.table || ((uintptr_t)g.table & 15) || !pow2(g.capacity) || g.capacity < 64) return -22;
+    if (!fk_type(g.type)) return -22;
+    if (g.how != STROM_JOIN_SEMI && g.how != STROM_JOIN_ANTI) return -22;
+    if (g.kout < -1 || g.kout >= STROM_JOIN_MAX_LEGS) return -22;
+    if (g.kout >= 0) {
+      if (g.how == STROM_JOIN_ANTI || !d_kout) return -22;   // a row that stays matched nothing
+      if (outs & (1u << g.kout)) return -22;                 // one leg per code table
+      outs |= 1u << g.kout;
+    }
+  }
+  if (!d_fk || !nbatches || !d_src || !d_dst || ((uintptr_t)d_src & 7) || ((uintptr_t)d_dst & 7))
+    return -22;
+  if (!nwords) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  switch (legs.nlegs) {
+    case 1: return launch_star<1>(legs, d_fk, nbatches, nwords, d_src, d_dst, d_kout, d_count, st);
+    case 2: return launch_star<2>(legs, d_fk, nbatches, nwords, d_src, d_dst, d_kout, d_count, st);
+    case 3: return launch_star<3>(legs, d_fk, nbatches, nwords, d_src, d_dst, d_kout, d_count, st);
+    default: return launch_star<4>(legs, d_fk, nbatches, nwords, d_src, d_dst, d_kout, d_count, st);
+  }
 }

@@ -203,6 +203,17 @@ class GroupKeys(C.Structure):
     _fields_ = [("nkeys", C.c_uint32), ("reserved", C.c_uint32), ("k", GroupKey * 4)]
 
 
+class JoinLeg(C.Structure):
+    """strom_join_leg: one dimension table of a star join."""
+    _fields_ = [("table", C.c_void_p), ("capacity", C.c_uint64), ("type", C.c_uint32),
+                ("how", C.c_uint32), ("kout", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class JoinLegs(C.Structure):
+    """strom_join_legs, passed by value to strom_column_join_star."""
+    _fields_ = [("nlegs", C.c_uint32), ("reserved", C.c_uint32), ("leg", JoinLeg * 4)]
+
+
 # ----------------------------------------------------------------- loading
 _lib = None
 _lock = threading.Lock()
@@ -341,6 +352,8 @@ _SIGS = {
     "strom_column_join": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
                                     C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "strom_column_join_star": (C.c_int, [JoinLegs, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "strom_group_capacity": (C.c_uint64, [C.c_uint64]),
     "strom_group_init": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "strom_group_codes": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,

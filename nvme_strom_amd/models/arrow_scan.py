@@ -34,7 +34,7 @@ import os
 import struct
 import time
 from dataclasses import dataclass, field, replace
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -197,6 +197,45 @@ class Join:
         self.col, self.table, self.how = str(col), table, how
 
 
+class StarJoin:
+    """``join=StarJoin(Join("cust", customers), Join("part", parts, "anti"), ...)``:
+    a star join, one to four Join legs applied in one probe launch per group
+    (strom_column_join_star): a row is kept if every leg keeps it.  The result
+    does not depend on the order of the legs; the order is the probe order, and
+    a row an earlier leg dropped costs the later ones nothing, so the most
+    selective leg goes first.  The fk columns may differ in type; a column or a
+    JoinTable may serve several legs.  ``dim[attr]`` in ``project=`` / ``by=`` /
+    ``HashBy([...])`` belongs to the one semi leg whose table is ``dim``."""
+
+    def __init__(self, *joins):
+        if len(joins) == 1 and isinstance(joins[0], (list, tuple)):
+            joins = tuple(joins[0])
+        if not joins:
+            raise ValueError("StarJoin: at least one Join leg")
+        if len(joins) > J.MAX_LEGS:
+            raise NotImplementedError(f"StarJoin of {len(joins)} legs: at most {J.MAX_LEGS} tables "
+                                      "are probed in one pass")
+        for j in joins:
+            if not isinstance(j, Join):
+                raise TypeError("StarJoin: every leg is a Join")
+        self.legs: Tuple[Join, ...] = tuple(joins)
+
+    def __repr__(self) -> str:
+        return "StarJoin(" + ", ".join(f"{j.col} {j.how}" for j in self.legs) + ")"
+
+
+def _legs(join) -> Tuple[Join, ...]:
+    """The legs of a checked ``join=``: none, the one Join, a StarJoin's."""
+    if join is None:
+        return ()
+    return join.legs if isinstance(join, StarJoin) else (join,)
+
+
+def _leg_of(join, attr: JoinAttr) -> int:
+    """The leg whose table carries ``attr`` (checked by _check_join)."""
+    return next(i for i, j in enumerate(_legs(join)) if j.table is attr.table)
+
+
 class HashBy:
     """``by=HashBy("customer_id", groups=1 << 20)``: GROUP BY an ordinary
     integer column (int8-int64, uint8-uint64 over its whole range, or a date /
@@ -209,7 +248,8 @@ class HashBy:
 
     ``HashBy(["region", "day"], groups)`` — a list or tuple, also of one — is
     ``GROUP BY region, day``: up to four components, each such a column or
-    one attribute of the scan's semi-join (``dim["category"]``), packed into
+    an attribute of a semi-join leg of the scan (``dim["category"]``: one per
+    JoinTable, of different tables with ``join=StarJoin(...)``), packed into
     the table's one 64-bit key word (ops/colgroup.KeySpec).  A column takes
     its storage width, one bit more when any record batch of the file has
     nulls in it; an attribute takes ceil(log2(number of its values)) bits.
@@ -236,9 +276,10 @@ class HashBy:
             for n in names:
                 if names.count(n) > 1:
                     raise ValueError(f"HashBy: {n[-1]!r} appears twice")
-            if sum(isinstance(c, JoinAttr) for c in comps) > 1:
-                raise NotImplementedError("HashBy: one JoinTable attribute per key (the probe "
-                                          "writes one attribute's codes)")
+            tabs = [id(c.table) for c in comps if isinstance(c, JoinAttr)]
+            if len(set(tabs)) < len(tabs):
+                raise NotImplementedError("HashBy: one JoinTable attribute per JoinTable (the "
+                                          "probe writes one attribute's codes per leg)")
             cols = [c for c in comps if not isinstance(c, JoinAttr)]
             for n, b in (bits or {}).items():
                 if n not in cols:
@@ -247,16 +288,20 @@ class HashBy:
                     raise ValueError(f"bits={b!r} for {n}: 1 <= bits <= its storage width")
                 self.bits[n] = int(b)
             self.comps = comps
-            self.col = tuple(c.name if isinstance(c, JoinAttr) else c for c in comps)
+            # a name that two components carry (attributes of different tables,
+            # or an attribute and a column) is qualified by its position
+            plain = [c.name if isinstance(c, JoinAttr) else c for c in comps]
+            self.col = tuple(f"{n}[{i}]" if plain.count(n) > 1 and isinstance(c, JoinAttr) else n
+                             for i, (n, c) in enumerate(zip(plain, comps)))
         else:
             if bits:
                 raise ValueError("bits= belongs to a list of key columns")
             self.col = str(col)
 
     @property
-    def attr(self) -> Optional[JoinAttr]:
-        """The JoinTable attribute among the components, if any."""
-        return next((c for c in self.comps or [] if isinstance(c, JoinAttr)), None)
+    def attrs(self) -> List[JoinAttr]:
+        """The JoinTable attributes among the components."""
+        return [c for c in self.comps or [] if isinstance(c, JoinAttr)]
 
     def __repr__(self) -> str:
         if self.comps is not None:
@@ -265,29 +310,36 @@ class HashBy:
         return f"HashBy({self.col!r}, groups={self.groups})"
 
 
-def _check_join(meta: ArrowFile, join, attr) -> Optional[Join]:
-    """Validate ``join=`` and the JoinAttr of ``by=`` / ``project=`` (or
-    None) against the schema."""
+def _check_join(meta: ArrowFile, join, attrs):
+    """Validate ``join=`` (a Join, a StarJoin or None) and the JoinAttrs of
+    ``by=`` / ``project=`` (one, a list or None) against the schema."""
+    attrs = [] if attrs is None else ([attrs] if isinstance(attrs, JoinAttr) else list(attrs))
     if isinstance(join, (list, tuple)):
-        raise NotImplementedError("one join per scan (a list of joins is not supported)")
+        raise NotImplementedError("one join per scan (a list of joins is not supported; "
+                                  "join=StarJoin(...) probes several tables in one pass)")
     if join is None:
-        if attr is not None:
-            raise ValueError(f"{attr!r} needs join= with its JoinTable")
+        if attrs:
+            raise ValueError(f"{attrs[0]!r} needs join= with its JoinTable")
         return None
-    if not isinstance(join, Join):
-        raise TypeError("join=: a Join")
+    if not isinstance(join, (Join, StarJoin)):
+        raise TypeError("join=: a Join or a StarJoin")
     schema = {c.name: c for c in meta.schema}
-    if join.col not in schema:
-        raise ValueError(f"no column {join.col!r}")
-    c = schema[join.col]
-    if c.dictionary is not None or c.kind != "int" or c.storage not in J.FK_CODE:
-        kind = "dictionary-encoded" if c.dictionary is not None else c.kind
-        raise NotImplementedError(f"join on {join.col}: {kind} columns are not joined "
-                                  "(integer columns are)")
-    if attr is not None:
-        if attr.table is not join.table:
+    for leg in _legs(join):
+        if leg.col not in schema:
+            raise ValueError(f"no column {leg.col!r}")
+        c = schema[leg.col]
+        if c.dictionary is not None or c.kind != "int" or c.storage not in J.FK_CODE:
+            kind = "dictionary-encoded" if c.dictionary is not None else c.kind
+            raise NotImplementedError(f"join on {leg.col}: {kind} columns are not joined "
+                                      "(integer columns are)")
+    for attr in attrs:
+        mine = [leg for leg in _legs(join) if leg.table is attr.table]
+        if not mine:
             raise ValueError(f"{attr!r} belongs to another JoinTable than the one in join=")
-        if join.how == "anti":
+        if len(mine) > 1:
+            raise ValueError(f"{attr!r} is ambiguous: its JoinTable is in {len(mine)} legs of "
+                             "the StarJoin (on " + ", ".join(leg.col for leg in mine) + ")")
+        if mine[0].how == "anti":
             raise ValueError(f"{attr!r} with how='anti': the rows an anti-join keeps matched "
                              "nothing")
     return join
@@ -311,13 +363,22 @@ class ScanOut:
 
 
 @dataclass
-class _JoinRun:
-    """A scan's join as _compute sees it."""
+class _LegRun:
+    """One leg of a scan's join as _compute sees it."""
     col: int                      # plan column of the foreign key
     code: int                     # its STROM_COL_* storage type
     how: str
     dev: J.DeviceTable
     attr: Optional[str] = None    # attribute whose codes the probe writes
+    buf: int = -1                 # star: which of the slot's leg buffers takes them
+
+
+@dataclass
+class _JoinRun:
+    """A scan's join as _compute sees it: one leg (join=Join: the
+    strom_column_join path) or a StarJoin's, all in one launch."""
+    legs: List[_LegRun]
+    star: bool = False
 
 
 @dataclass
@@ -327,8 +388,10 @@ class _HashRun:
     code: int                     # its STROM_COL_* storage type
     dev: G.DeviceGroups
     # a composite key (dev.spec): the plan column of each component, None for
-    # the join attribute, whose codes the probe leaves in the slot's key buffer
+    # a join attribute, whose codes the probe leaves in the slot's key buffer
+    # (join=Join) or in the leg buffer ``bufs`` names (join=StarJoin)
     cols: Optional[List[Optional[int]]] = None
+    bufs: Optional[List[int]] = None
 
 
 @dataclass
@@ -470,6 +533,8 @@ class _Slot:
     keep: List[torch.Tensor] = field(default_factory=list)
     pin: Optional[torch.Tensor] = None     # pinned arena for the group's tables
     keybuf: Optional[torch.Tensor] = None  # int32 per row: the joined attribute's code
+    # a StarJoin's attribute legs: one more such buffer each, reused like keybuf
+    legbuf: List[torch.Tensor] = field(default_factory=list)
     pin_off: int = 0
 
 
@@ -1001,11 +1066,16 @@ class ArrowScan:
             d_codes = None
             if run.join is not None:
                 bitmap, d_codes = self._probe(s, g, t, run.join, bitmap)
+                if run.join.star and d_codes is not None:
+                    # project= / by=dim[attr] / top carry one attribute: leg
+                    # buffer 0 (a HashBy of several reads them by its own tables)
+                    d_codes = d_codes[0]
             if run.hash is not None:
                 bitmap, d_codes = self._group_codes(s, g, t, run.hash, bitmap)
             run.marks.append((k, "quals_queued", time.perf_counter()))
             # emit tables: the strom_filter_batch prefix of the qual tables
-            any_col = spec[0][0][0] if spec else (run.join.col if run.join is not None else 0)
+            any_col = spec[0][0][0] if spec else (run.join.legs[0].col if run.join is not None
+                                                  else 0)
             d_rows = t.dev5(any_col)
             args = d_proj = slabs = None
             if run.top is not None:
@@ -1098,13 +1168,25 @@ class ArrowScan:
         s.keep.append(bitmap)
         return bitmap
 
-    def _code_table(self, s: _Slot, g: _Group) -> np.ndarray:
-        """The batch table of the slot's key buffer (int32 per row of the
-        bitmap, allocated on first use): batch b's codes at row word_base * 64."""
-        if s.keybuf is None or s.keybuf.numel() < s.bitmap.numel() * 64:
-            s.keybuf = torch.empty(s.bitmap.numel() * 64, dtype=torch.int32, device=self.device)
+    def _code_table(self, s: _Slot, g: _Group, leg: int = -1) -> np.ndarray:
+        """The batch table of the slot's key buffer, or of its buffer for the
+        codes of a StarJoin's attribute leg ``leg`` (int32 per row of the
+        bitmap, allocated on first use and kept for the slot's later groups):
+        batch b's codes at row word_base * 64."""
+        rows = s.bitmap.numel() * 64
+        new = lambda: torch.empty(rows, dtype=torch.int32, device=self.device)
+        if leg < 0:
+            if s.keybuf is None or s.keybuf.numel() < rows:
+                s.keybuf = new()
+            buf = s.keybuf
+        else:
+            while len(s.legbuf) <= leg:
+                s.legbuf.append(new())
+            if s.legbuf[leg].numel() < rows:
+                s.legbuf[leg] = new()
+            buf = s.legbuf[leg]
         c5 = g.table[:, :BATCH_FIELDS].copy()
-        c5[:, 0] = s.keybuf.data_ptr() + g.table[:, 3] * 256
+        c5[:, 0] = buf.data_ptr() + g.table[:, 3] * 256
         c5[:, 1] = 0
         return c5
 
@@ -1114,14 +1196,34 @@ class ArrowScan:
         the selection's): the fk's batch table and, when an attribute is
         wanted, the table of the slot's key buffer go up in one copy.  Returns
         (the selection's bitmap, the latter table on the device or None)."""
-        both = [t.host5(jn.col)]
-        if jn.attr is not None:
+        if jn.star:
+            return self._probe_star(s, g, t, jn, bitmap)
+        leg = jn.legs[0]
+        both = [t.host5(leg.col)]
+        if leg.attr is not None:
             both.append(self._code_table(s, g))
         d_j = self._upload(s, np.stack(both))
         s.keep.append(d_j)
-        d_kout = d_j[1] if jn.attr is not None else None
-        J.probe(jn.dev, jn.code, d_j[0], g.words, bitmap, s.bitmap, s.count,
-                how=J.HOW[jn.how], key_out=d_kout, stream=s.stream)
+        d_kout = d_j[1] if leg.attr is not None else None
+        J.probe(leg.dev, leg.code, d_j[0], g.words, bitmap, s.bitmap, s.count,
+                how=J.HOW[leg.how], key_out=d_kout, stream=s.stream)
+        return s.bitmap, d_kout
+
+    def _probe_star(self, s: _Slot, g: _Group, t: _Tables, jn: _JoinRun,
+                    bitmap: torch.Tensor) -> tuple:
+        """join=StarJoin: every leg's fk table and the tables of the attribute
+        legs' code buffers in one copy, every leg in one launch.  Returns (the
+        selection's bitmap, the code buffers' tables on the device
+        (buffers, batches, 5) or None)."""
+        nout = sum(leg.buf >= 0 for leg in jn.legs)
+        tabs = [t.host5(leg.col) for leg in jn.legs] + \
+            [self._code_table(s, g, j) for j in range(nout)]
+        d_j = self._upload(s, np.stack(tabs))
+        s.keep.append(d_j)
+        d_kout = d_j[len(jn.legs):] if nout else None
+        J.probe_star([(leg.dev, leg.code, J.HOW[leg.how], leg.buf) for leg in jn.legs],
+                     d_j[:len(jn.legs)], g.words, bitmap, s.bitmap, s.count, key_out=d_kout,
+                     stream=s.stream)
         return s.bitmap, d_kout
 
     def _group_codes(self, s: _Slot, g: _Group, t: _Tables, hs: _HashRun,
@@ -1133,10 +1235,12 @@ class ArrowScan:
         c5 = self._code_table(s, g)
         # a composite key: every component's table, the join attribute's
         # being the code buffers' own (the launch runs in place there: a lane
-        # reads its row's components before it stores the row's code); then,
-        # in the same copy, the code buffers'
+        # reads its row's components before it stores the row's code) or, with
+        # join=StarJoin, each attribute leg's buffer; then, in the same copy,
+        # the code buffers'
         k5 = [t.host5(hs.col)] if hs.cols is None else \
-            [c5 if c is None else t.host5(c) for c in hs.cols]
+            [(c5 if b < 0 else self._code_table(s, g, b)) if c is None else t.host5(c)
+             for c, b in zip(hs.cols, hs.bufs)]
         d_h = self._upload(s, np.stack(k5 + [c5]))
         s.keep.append(d_h)
         if hs.cols is None:
@@ -1247,17 +1351,27 @@ class ArrowScan:
             self._compiled[key] = _compile_pred(p, col, self.dictionary)
         return self._compiled[key]
 
-    def _join_run(self, join: Join, names: List[str], attr: Optional[JoinAttr]) -> _JoinRun:
-        td = join.table.device
+    def _join_run(self, join, names: List[str], attrs) -> _JoinRun:
+        """The checked ``join=`` with the attributes the scan wants written
+        (one, a list or None; a StarJoin's attribute legs get the slot's leg
+        buffers 0, 1, ... in the order of ``attrs``)."""
+        attrs = [] if attrs is None else ([attrs] if isinstance(attrs, JoinAttr) else list(attrs))
         # "cuda" and "cuda:<current device>" are the same place
         idx = lambda d: d.index if d.index is not None else torch.cuda.current_device()
-        if td is None or td.type != self.device.type or (td != self.device and
-                                                          idx(td) != idx(self.device)):
-            raise ValueError(f"JoinTable on {td}, scan on {self.device}")
-        col = self.meta.schema[self.meta.column_index(join.col)]
-        name = attr.name if attr is not None else None
-        return _JoinRun(names.index(join.col), J.FK_CODE[col.storage], join.how,
-                        join.table._device_table(name), name)
+        star = isinstance(join, StarJoin)
+        legs = []
+        for i, leg in enumerate(_legs(join)):
+            td = leg.table.device
+            if td is None or td.type != self.device.type or (td != self.device and
+                                                              idx(td) != idx(self.device)):
+                raise ValueError(f"JoinTable on {td}, scan on {self.device}")
+            col = self.meta.schema[self.meta.column_index(leg.col)]
+            at = [k for k, a in enumerate(attrs) if _leg_of(join, a) == i]
+            name = attrs[at[0]].name if at else None
+            legs.append(_LegRun(names.index(leg.col), J.FK_CODE[col.storage], leg.how,
+                                leg.table._device_table(name), name,
+                                at[0] if at and star else -1))
+        return _JoinRun(legs, star)
 
     def _resolve(self, names: List[str], batches: Optional[Tuple[int, int]]) -> tuple:
         """(Column metas, rows, groups) of a scan of ``names`` over ``batches``,
@@ -1323,7 +1437,7 @@ class ArrowScan:
                 "total_s": time.perf_counter() - t0}
 
     def scan_where(self, quals, project=None, batches: Optional[Tuple[int, int]] = None,
-                   join: Optional[Join] = None) -> ScanOut:
+                   join: Union[Join, StarJoin, None] = None) -> ScanOut:
         """Row ids (int64, file order) of the rows every qualifier selects —
         a PG-Strom qualifier list.  ``quals`` items: ``(name, lo, hi)``
         ranges, ``(name, op, value)`` / ``P(name) <op> value`` predicates,
@@ -1345,7 +1459,9 @@ class ArrowScan:
         (csrc/kernels/coljoin.hip) on the slot's stream after the qualifier
         list, which may then be empty.  ``project=dim[attr]`` gathers the
         joined attribute's code per selected row (``ScanOut.dictionary``
-        holds the codes' values)."""
+        holds the codes' values).  ``join=StarJoin(Join(...), Join(...), ...)``
+        applies up to four such legs in that one launch (a row is kept if every
+        leg keeps it); ``dim[attr]`` then names the leg whose table is ``dim``."""
         pattr = project if isinstance(project, JoinAttr) else None
         join = _check_join(self.meta, join, pattr)
         if pattr is not None:
@@ -1416,7 +1532,7 @@ class ArrowScan:
                        column=pmeta, dictionary=pdict, offsets=offsets)
 
     def aggregate(self, quals, aggs, by=None, batches: Optional[Tuple[int, int]] = None,
-                  join: Optional[Join] = None) -> "AggOut":
+                  join: Union[Join, StarJoin, None] = None) -> "AggOut":
         """``SELECT by, aggs... WHERE quals GROUP BY by`` in one pass over
         the file: the qualifier, aggregated and key columns are read and
         decoded once per group, the qualifier kernels leave the selection
@@ -1448,11 +1564,14 @@ class ArrowScan:
         joined rows are aggregated, and ``by=dim[attr]`` groups them by an
         attribute of the JoinTable — the probe writes each row's attribute
         code into the slot's key buffer and the aggregate kernels take it as
-        their key column.  See AggOut."""
+        their key column.  With ``join=StarJoin(...)`` each attribute leg
+        writes a code buffer of its own, and ``HashBy([dimA[x], dimB[y], ...])``
+        groups by attributes of different JoinTables.  See AggOut."""
         t0 = time.perf_counter()
         battr = by if isinstance(by, JoinAttr) else None
         hb = by if isinstance(by, HashBy) else None
-        join = _check_join(self.meta, join, battr if hb is None else hb.attr)
+        jattrs = battr if hb is None else hb.attrs
+        join = _check_join(self.meta, join, jattrs)
         if battr is not None or hb is not None:
             by = None
         cl = clauses(quals) if quals else []
@@ -1477,7 +1596,7 @@ class ArrowScan:
         agg.key_col = names.index(by) if by is not None else None
         run = _Run(self._zero(), self._zero(), agg=agg)
         if join is not None:
-            run.join = self._join_run(join, names, battr if hb is None else hb.attr)
+            run.join = self._join_run(join, names, jattrs)
         # the block is initialised on the emit stream, where the reduces follow
         es = self._emit_stream()
         with torch.cuda.stream(es):
@@ -1489,8 +1608,13 @@ class ArrowScan:
                 dev = G.DeviceGroups(agg.layout.entries, hb.groups, self.device,
                                      agg.hash_unsigned, stream=es, spec=agg.keyspec)
         if agg.keyspec is not None:
+            # a StarJoin's attribute legs write leg buffers 0, 1, ... in the
+            # order of the components; a Join's one attribute the key buffer
+            star = isinstance(join, StarJoin)
             run.hash = _HashRun(-1, 0, dev, [None if isinstance(c, JoinAttr) else
-                                             names.index(c) for c in hb.comps])
+                                             names.index(c) for c in hb.comps],
+                                [hb.attrs.index(c) if star and isinstance(c, JoinAttr) else -1
+                                 for c in hb.comps])
         elif hb is not None:
             kc = self.meta.schema[self.meta.column_index(hb.col)]
             run.hash = _HashRun(names.index(hb.col), G.KEY_CODE[kc.storage], dev)
@@ -1516,14 +1640,14 @@ class ArrowScan:
         return _hash_out(agg, found, nrows, secs, **moved)
 
     def host_aggregate(self, quals, aggs, by=None, batches: Optional[Tuple[int, int]] = None,
-                       join: Optional[Join] = None) -> "AggOut":
+                       join: Union[Join, StarJoin, None] = None) -> "AggOut":
         """The same query on the CPU (host_scan_where's path plus the
         aggregate kernels' numpy twin, ops/colagg.py)."""
         return host_aggregate(self.path, quals, aggs, by, batches, meta=self.meta,
                               dicts=self._dicts, join=join)
 
     def top(self, quals, order_by: str, k: int, descending: bool = False, project=None,
-            batches: Optional[Tuple[int, int]] = None, join: Optional[Join] = None) -> "TopOut":
+            batches: Optional[Tuple[int, int]] = None, join: Union[Join, StarJoin, None] = None) -> "TopOut":
         """``SELECT row, order_by[, project] WHERE quals ORDER BY order_by
         [DESC] LIMIT k`` in one pass: the first ``k`` of the selected rows by
         (a value before a NaN before a null — in both directions —, the value
@@ -1594,7 +1718,7 @@ class ArrowScan:
 
     def host_top(self, quals, order_by: str, k: int, descending: bool = False, project=None,
                  batches: Optional[Tuple[int, int]] = None,
-                 join: Optional[Join] = None) -> "TopOut":
+                 join: Union[Join, StarJoin, None] = None) -> "TopOut":
         """The same query on the CPU (the host twins' scan, the candidates'
         numpy twin, ops/coltopk.py)."""
         return host_top(self.path, quals, order_by, k, descending, project, batches,
@@ -1609,7 +1733,7 @@ class ArrowScan:
     filter = scan
 
     def host_scan_where(self, quals, project=None, batches: Optional[Tuple[int, int]] = None,
-                        join: Optional[Join] = None) -> "HostScanOut":
+                        join: Union[Join, StarJoin, None] = None) -> "HostScanOut":
         """The same query on the CPU (buffers read with pread, decoded by
         the decoders' host twins, predicates by colpred's numpy twin, the
         join by coljoin's)."""
@@ -1650,10 +1774,10 @@ def _host_join(join: Join, v, ok, m: np.ndarray):
     return (m & ~match if join.how == "anti" else m & match), row
 
 
-def _scanned(cl, join: Optional[Join], more: Sequence[str]) -> List[str]:
-    """The columns a scan reads, each once: the qualifiers', the foreign key,
-    then ``more`` — the order of the plan's columns."""
-    return list(dict.fromkeys([p.col for c in cl for p in c] + ([join.col] if join else []) +
+def _scanned(cl, join, more: Sequence[str]) -> List[str]:
+    """The columns a scan reads, each once: the qualifiers', the foreign keys
+    of the join's legs, then ``more`` — the order of the plan's columns."""
+    return list(dict.fromkeys([p.col for c in cl for p in c] + [j.col for j in _legs(join)] +
                               list(more)))
 
 
@@ -1672,12 +1796,13 @@ def _compile_pred(p: Pred, col: Column, dictionary) -> Compiled:
     return compile_pred(p, col, dic)
 
 
-def _host_batches(path: str, meta: ArrowFile, dicts: dict, cl, join: Optional[Join],
+def _host_batches(path: str, meta: ArrowFile, dicts: dict, cl, join,
                   more: Sequence[str], batches: Optional[Tuple[int, int]],
                   values=lambda name: True):
     """The host twins' scan: per record batch of the range (batch index,
     batch, {column: (values, validity)}, the rows the CNF ``cl`` and the join
-    select, the join's build row per row or None).  The qualifier and join
+    select, per leg of the join its build row per row, or None).  The legs are
+    applied in turn, each to the rows the ones before it left.  The qualifier and join
     columns and ``more`` are read and decoded; a column of ``more`` for which
     ``values(name)`` is false gets its validity alone (values None)."""
     schema = {c.name: (i, c) for i, c in enumerate(meta.schema)}
@@ -1719,7 +1844,10 @@ def _host_batches(path: str, meta: ArrowFile, dicts: dict, cl, join: Optional[Jo
                 m &= cm
             jrow = None
             if join is not None:
-                m, jrow = _host_join(join, *data[join.col], m)
+                jrow = []
+                for leg in _legs(join):
+                    m, row = _host_join(leg, *data[leg.col], m)
+                    jrow.append(row)
             yield bi, b, data, m, jrow
     finally:
         src.close()
@@ -1727,7 +1855,7 @@ def _host_batches(path: str, meta: ArrowFile, dicts: dict, cl, join: Optional[Jo
 
 def host_scan_where(path: str, quals, project=None,
                     batches: Optional[Tuple[int, int]] = None, meta: Optional[ArrowFile] = None,
-                    dicts: Optional[dict] = None, join: Optional[Join] = None) -> HostScanOut:
+                    dicts: Optional[dict] = None, join: Union[Join, StarJoin, None] = None) -> HostScanOut:
     """ArrowScan.scan_where on the CPU: the same metadata, the same
     compiled predicates (ops/colpred.py), evaluated by the kernel's numpy
     twin over buffers decoded by the GPU decoders' host twins.  The
@@ -1742,13 +1870,14 @@ def host_scan_where(path: str, quals, project=None,
     base = np.concatenate([[0], np.cumsum(meta.rows)]).astype(np.int64)
     nrows = 0
     ids, vals, valid = [], [], []
+    pleg = _leg_of(join, pattr) if pattr is not None else None
     for bi, b, data, m, jrow in _host_batches(path, meta, dicts, cl, join,
                                               [project] if project else [], batches):
         nrows += b.length
         sel = np.flatnonzero(m)
         ids.append(sel + base[bi])
         if pattr is not None:
-            vals.append(pattr.codes[jrow[sel]] if len(pattr.codes) else
+            vals.append(pattr.codes[jrow[pleg][sel]] if len(pattr.codes) else
                         np.zeros(0, np.int32))
             valid.append(np.ones(len(sel), bool))
         if project:
@@ -1852,12 +1981,14 @@ def _key_spec(meta: ArrowFile, hb: HashBy) -> Tuple[G.KeySpec, list]:
     range is scanned, so that results of its ranges pack alike and merge."""
     schema = {c.name: c for c in meta.schema}
     comps, attrs = [], []
-    for c in hb.comps:
+    for c, shown in zip(hb.comps, hb.col):
         if isinstance(c, JoinAttr):
             nv = max(len(c.values), 1)
             # codes 0 .. nv - 1, never negative: an unsigned field over the
             # probe's int32 buffer
-            comps.append((c.name, "u4", max(1, int(nv - 1).bit_length()), False))
+            # ``shown``: the attribute's name, qualified when another component
+            # carries the same
+            comps.append((shown, "u4", max(1, int(nv - 1).bit_length()), False))
             attrs.append(list(c.values))
             continue
         k = _hash_key(schema, c, f"..., {c}, ...")
@@ -2120,7 +2251,7 @@ def _hash_out(spec: _AggSpec, found: G.Groups, rows: int, seconds: Dict[str, flo
 
 def host_aggregate(path: str, quals, aggs, by=None,
                    batches: Optional[Tuple[int, int]] = None, meta: Optional[ArrowFile] = None,
-                   dicts: Optional[dict] = None, join: Optional[Join] = None) -> AggOut:
+                   dicts: Optional[dict] = None, join: Union[Join, StarJoin, None] = None) -> AggOut:
     """ArrowScan.aggregate on the CPU: buffers read with pread and decoded
     by the decoders' host twins, the qualifiers by colpred's numpy twin, the
     aggregates by colagg's.  The reference point for the GPU path and the
@@ -2131,7 +2262,7 @@ def host_aggregate(path: str, quals, aggs, by=None,
     cl = clauses(quals) if quals else []
     battr = by if isinstance(by, JoinAttr) else None
     hb = by if isinstance(by, HashBy) else None
-    join = _check_join(meta, join, battr if hb is None else hb.attr)
+    join = _check_join(meta, join, battr if hb is None else hb.attrs)
     if battr is not None or hb is not None:
         by = None
     spec = _agg_spec(meta, aggs, by, lambda name: _dictionary(meta, path, dicts, name), battr, hb)
@@ -2149,8 +2280,8 @@ def host_aggregate(path: str, quals, aggs, by=None,
         nrows += b.length
         key = None
         if battr is not None:
-            key = (np.where(m, battr.codes[jrow] if len(battr.codes) else 0, 0)
-                   .astype(np.int32), None)
+            key = (np.where(m, battr.codes[jrow[_leg_of(join, battr)]] if len(battr.codes)
+                            else 0, 0).astype(np.int32), None)
         if by is not None:
             kv, kok = data[by]
             kv = np.asarray(kv)
@@ -2163,8 +2294,8 @@ def host_aggregate(path: str, quals, aggs, by=None,
             kcols, koks = [], []
             for c in hb.comps:
                 if isinstance(c, JoinAttr):
-                    kcols.append(np.where(m, c.codes[jrow] if len(c.codes) else 0, 0)
-                                 .astype(np.uint32))
+                    kcols.append(np.where(m, c.codes[jrow[_leg_of(join, c)]] if len(c.codes)
+                                          else 0, 0).astype(np.uint32))
                     koks.append(None)
                 else:
                     kcols.append(np.asarray(data[c][0]))
@@ -2306,7 +2437,7 @@ def _top_out(spec: _TopSpec, ent: np.ndarray, nrows: int, selected: int,
 
 def host_top(path: str, quals, order_by: str, k: int, descending: bool = False, project=None,
              batches: Optional[Tuple[int, int]] = None, meta: Optional[ArrowFile] = None,
-             dicts: Optional[dict] = None, join: Optional[Join] = None) -> TopOut:
+             dicts: Optional[dict] = None, join: Union[Join, StarJoin, None] = None) -> TopOut:
     """ArrowScan.top on the CPU: the host twins' scan, then numpy ``lexsort``
     on (class, key, row) of the candidates (ops/coltopk.py), batch by batch.
     The reference point for the GPU path and the same answer without one."""
@@ -2333,7 +2464,8 @@ def host_top(path: str, quals, order_by: str, k: int, descending: bool = False, 
         v, ok = data[order_by]
         pay = pok = None
         if pattr is not None:
-            pay = pattr.codes[jrow[sel]] if len(pattr.codes) else np.zeros(0, np.int32)
+            pay = pattr.codes[jrow[_leg_of(join, pattr)][sel]] if len(pattr.codes) else \
+                np.zeros(0, np.int32)
         elif project:
             pv, pk = data[project]
             pay, pok = np.asarray(pv)[sel], (None if pk is None else pk[sel])

@@ -299,3 +299,117 @@ def probe(table: DeviceTable, fk_code: int, fk, nwords: int, src, dst, count, ho
                                   fk.shape[0], nwords, ptr(src), ptr(dst),
                                   ptr(key_out) if key_out is not None else 0, ptr(count),
                                   stream_handle(stream)), "column_join")
+
+
+# ------------------------------------------------------------ star join
+MAX_LEGS = 4
+
+
+def _how(how) -> int:
+    """SEMI / ANTI of "semi" / "anti" or the code itself."""
+    return HOW[how] if isinstance(how, str) and how in HOW else how
+
+
+def _check_legs(legs, ntables: int) -> None:
+    """The rules of strom_column_join_star's legs, for the wrapper and the twin:
+    ``legs`` items are (table, ..., how, kout)."""
+    if not 1 <= len(legs) <= MAX_LEGS:
+        raise ValueError(f"a star join has 1 .. {MAX_LEGS} legs")
+    seen = set()
+    for leg in legs:
+        how, kout = leg[-2], leg[-1]
+        if how not in (SEMI, ANTI):
+            raise ValueError(f"leg how={how!r}: SEMI or ANTI")
+        if kout is None or kout < 0:
+            continue
+        if how == ANTI:
+            raise ValueError("an anti-join leg has no key output")
+        if kout >= ntables or kout in seen:
+            raise ValueError("kout: the index of a code table, each used by one leg")
+        seen.add(kout)
+
+
+def host_probe_star(legs: Sequence[tuple], fk_batches: Sequence[Sequence[tuple]], src: np.ndarray,
+                    key_out: Optional[List[List[np.ndarray]]] = None):
+    """strom_column_join_star's result over record batches.  ``legs``: per
+    leg (HostTable, how SEMI / ANTI or its name, kout: index into ``key_out`` or -1);
+    ``fk_batches[i]``: leg i's list of (fk values, valid bool or None), one per
+    batch, batch b on fresh bitmap words; ``src`` the source words (bits beyond
+    a batch's rows are ignored); ``key_out[j]``: one int32 array per batch.
+    Returns (destination words uint64, key output copied): a leg's payload is
+    stored for exactly the rows of the destination, every other element of a
+    code buffer is left as it was."""
+    legs = [(t, _how(how), -1 if kout is None else int(kout)) for t, how, kout in legs]
+    _check_legs(legs, len(key_out) if key_out is not None else 0)
+    if len(fk_batches) != len(legs) or any(len(f) != len(fk_batches[0]) for f in fk_batches):
+        raise ValueError("fk_batches: one list of the same batches per leg")
+    src = np.asarray(src).view(np.uint64)
+    dst = np.zeros(len(src), np.uint64)
+    out = [[k.copy() for k in tab] for tab in key_out] if key_out is not None else None
+    w0 = 0
+    for b in range(len(fk_batches[0])):
+        n = len(fk_batches[0][b][0])
+        nw = (n + 63) // 64
+        cur = np.unpackbits(src[w0:w0 + nw].view(np.uint8), bitorder="little")[:n].astype(bool)
+        pays = []
+        for (t, how, _), fks in zip(legs, fk_batches):
+            v, ok = fks[b]
+            if len(v) != n:
+                raise ValueError("fk_batches: the legs' batches differ in rows")
+            keys, can = widen(v)
+            # a row an earlier leg dropped is not probed
+            act = cur & can & (np.ones(n, bool) if ok is None else np.asarray(ok, bool)[:n])
+            m, pay = host_lookup(t, keys, act)
+            cur = cur & ~m if how == ANTI else cur & m
+            pays.append(pay)
+        bits = np.zeros(nw * 64, np.uint8)
+        bits[:n] = cur
+        dst[w0:w0 + nw] = np.packbits(bits, bitorder="little").view(np.uint64)
+        for (_, _, kout), pay in zip(legs, pays):
+            if kout >= 0:
+                out[kout][b][:n][cur] = pay[cur]
+        w0 += nw
+    return dst, out
+
+
+def probe_star(legs: Sequence[tuple], fk_tables, nwords: int, src, dst, count, key_out=None,
+               stream=None) -> None:
+    """strom_column_join_star over a group: every leg in one walk of the
+    bitmap.  ``legs``: per leg (DeviceTable, fk storage code, how SEMI / ANTI,
+    kout: index of its code table in ``key_out`` or -1), in probe order;
+    ``fk_tables`` the legs' strom_filter_batch tables, contiguous int64
+    (len(legs), nbatches, 5) over the same batches; ``src`` / ``dst`` /
+    ``count`` as probe; ``key_out`` contiguous int64 (ntables, nbatches, 5),
+    values pointing to int32 buffers (semi legs only)."""
+    import torch
+    from .._native import JoinLegs
+    from ._util import check, lib, ptr, require_cuda, stream_handle
+    from .colfilter import BATCH_FIELDS
+    legs = [(t, int(code), _how(how), -1 if kout is None else int(kout))
+            for t, code, how, kout in legs]
+    _check_legs(legs, key_out.shape[0] if key_out is not None else 0)
+    for t, name in ((fk_tables, "fk_tables"), (src, "src"), (dst, "dst"), (count, "count")):
+        require_cuda(t, name)
+    if fk_tables.dtype != torch.int64 or fk_tables.dim() != 3 or \
+            fk_tables.shape[0] != len(legs) or fk_tables.shape[2] != BATCH_FIELDS or \
+            not fk_tables.is_contiguous():
+        raise ValueError(f"fk_tables: contiguous int64 ({len(legs)}, n, 5)")
+    if key_out is not None:
+        require_cuda(key_out, "key_out")
+        if key_out.dtype != torch.int64 or key_out.dim() != 3 or \
+                key_out.shape[1:] != fk_tables.shape[1:] or not key_out.is_contiguous():
+            raise ValueError("key_out: contiguous int64 (tables, n, 5) of the same batches")
+    if src.numel() < nwords or dst.numel() < nwords:
+        raise ValueError("bitmap too small")
+    a = JoinLegs()
+    a.nlegs = len(legs)
+    for i, (t, code, how, kout) in enumerate(legs):
+        if code not in FK_CODE.values():
+            raise NotImplementedError(f"join on storage type {code}: integer columns are joined")
+        a.leg[i].table, a.leg[i].capacity = ptr(t.words), t.capacity
+        a.leg[i].type, a.leg[i].how, a.leg[i].kout = code, how, kout
+    if not nwords or not fk_tables.shape[1]:
+        return
+    check(lib().strom_column_join_star(a, ptr(fk_tables), fk_tables.shape[1], nwords, ptr(src),
+                                       ptr(dst), ptr(key_out) if key_out is not None else 0,
+                                       ptr(count), stream_handle(stream)), "column_join_star")

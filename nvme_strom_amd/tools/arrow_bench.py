@@ -405,6 +405,106 @@ def join_rows(path: str, fd: int, a, col) -> dict:
     return rows
 
 
+def star_row(path: str, fd: int, a, col) -> dict:
+    """``aggregate([x range], [count(*), sum(id)], by=HashBy([dimA["cat"],
+    dimB["cat"]]), join=StarJoin(Join("val", dimA), Join("id", dimB)))`` — two
+    dimensions probed in one pass, grouped by an attribute of each — against
+    the same answer through one join per scan: ``scan_where(project="id",
+    join=Join("val", dimA))`` and the same scan projecting ``val``, then
+    searchsorted, gather, bincount and index_add in torch.  dimA: 131,072 keys
+    of 64 categories; dimB: up to 2^20 of the file's ids, 16 categories.
+    ``--join-pairs`` alternated runs, the order flipped every pair, the file
+    evicted before every run; both verified against numpy."""
+    import torch
+
+    import nvme_strom_amd as S
+    from nvme_strom_amd.models.arrow_scan import ArrowScan, HashBy, Join, JoinTable, StarJoin
+    rng = np.random.default_rng(19)
+    quals = [("x", 0.25, 0.75)]
+    aggs = [("count", None), ("sum", "id")]
+    akeys = np.sort(rng.choice(1_000_000, 131_072, replace=False)).astype(np.int64)
+    bkeys = np.sort(rng.choice(a.rows, min(max(a.rows // 2, 1), 1 << 20),
+                               replace=False)).astype(np.int64)
+    dim_a = JoinTable(akeys, attrs={"cat": rng.integers(0, 64, len(akeys))}, device="cuda")
+    dim_b = JoinTable(bkeys, attrs={"cat": rng.integers(0, 16, len(bkeys))}, device="cuda")
+    na, nb = len(dim_a["cat"].values), len(dim_b["cat"].values)
+    d_akeys, d_bkeys = torch.from_numpy(akeys).cuda(), torch.from_numpy(bkeys).cuda()
+    d_acodes = torch.from_numpy(dim_a["cat"].codes.astype(np.int64)).cuda()
+    d_bcodes = torch.from_numpy(dim_b["cat"].codes.astype(np.int64)).cuda()
+    sc = ArrowScan(path, "cuda", slot_bytes=a.slot_mib << 20, nslots=a.nslots or None,
+                   chunk_sz=(a.chunk_kib << 10) or None)
+    star = StarJoin(Join("val", dim_a), Join("id", dim_b))
+    by = HashBy([dim_a["cat"], dim_b["cat"]], groups=na * nb)
+
+    def timed(fn):
+        S.evict_file(fd)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t, out
+
+    def one_pass():
+        return sc.aggregate(quals, aggs, by=by, join=star)
+
+    def two_scans():
+        ids = sc.scan_where(quals, project="id", join=Join("val", dim_a))
+        fk = sc.scan_where(quals, project="val", join=Join("val", dim_a))
+        ca = d_acodes[torch.searchsorted(d_akeys, fk.values)]
+        pos = torch.searchsorted(d_bkeys, ids.values).clamp_(max=len(bkeys) - 1)
+        hit = d_bkeys[pos] == ids.values
+        codes = ca[hit] * nb + d_bcodes[pos[hit]]
+        cnt = torch.bincount(codes, minlength=na * nb)
+        sm = torch.zeros(na * nb, dtype=torch.int64, device="cuda").index_add_(
+            0, codes, ids.values[hit])
+        return cnt.cpu().numpy(), sm.cpu().numpy(), fk.bytes_read + ids.bytes_read
+    try:
+        timed(one_pass), timed(two_scans)            # cold runs: plans, slots, code objects
+        star_s, two_s = [], []
+        for k in range(max(1, a.join_pairs)):
+            for what in (("star", "two") if k % 2 == 0 else ("two", "star")):
+                if what == "star":
+                    dt, sout = timed(one_pass)
+                    star_s.append(dt)
+                else:
+                    dt, (tcnt, tsum, tbytes) = timed(two_scans)
+                    two_s.append(dt)
+            _log(f"star pair {k}: one pass {star_s[-1] * 1e3:.1f} ms, two scans + torch "
+                 f"{two_s[-1] * 1e3:.1f} ms")
+    finally:
+        sc.close()
+        dim_a.close()
+        dim_b.close()
+    xv, xok = col("x")
+    m = (xv >= 0.25) & (xv <= 0.75)
+    if xok is not None:
+        m &= xok
+    val, ids = col("val")[0], col("id")[0]
+    m &= np.isin(val, akeys) & np.isin(ids, bkeys)
+    code = dim_a["cat"].codes[np.searchsorted(akeys, val[m])].astype(np.int64) * nb + \
+        dim_b["cat"].codes[np.searchsorted(bkeys, ids[m])]
+    want_cnt = np.bincount(code, minlength=na * nb)
+    want_sum = np.zeros(na * nb, np.int64)
+    np.add.at(want_sum, code, ids[m])
+    order = [dim_a["cat"].values.index(ka) * nb + dim_b["cat"].values.index(kb)
+             for ka, kb in sout.keys]
+    ok = bool(len(order) == int((want_cnt > 0).sum()) and
+              np.array_equal(sout.count_all, want_cnt[order]) and
+              np.array_equal(sout.get("sum", "id")[0], want_sum[order]) and
+              np.array_equal(tcnt, want_cnt) and np.array_equal(tsum, want_sum))
+    r = [x / y for x, y in zip(star_s, two_s)]
+    row = dict(aggs=[list(x) for x in aggs], keys=[len(akeys), len(bkeys)], categories=[na, nb],
+               selected=sout.selected, groups_found=len(sout.keys), verified=ok,
+               bytes_read=sout.bytes_read, two_scans_bytes_read=int(tbytes), pairs=len(r),
+               star_ms=[round(x * 1e3, 2) for x in star_s],
+               two_scans_torch_ms=[round(x * 1e3, 2) for x in two_s],
+               median_star_ms=round(float(np.median(star_s)) * 1e3, 2),
+               median_two_scans_torch_ms=round(float(np.median(two_s)) * 1e3, 2),
+               median_ratio=round(float(np.median(r)), 4),
+               min_ratio=round(min(r), 4), max_ratio=round(max(r), 4))
+    _log(json.dumps(row))
+    return row
+
+
 def hashagg_row(path: str, fd: int, a, col) -> dict:
     """``aggregate([x range], [count(*), sum(id), max(x)], by=HashBy("val",
     groups=1 << 20))`` — ``val`` has a million distinct values, an id-like
@@ -657,7 +757,8 @@ def main(argv=None) -> int:
     ap.add_argument("--agg-pairs", type=int, default=5)
     ap.add_argument("--join", action="store_true",
                     help="add the join rows: a semi-join scan alternated with the same scan "
-                         "under isin(), and aggregate(join=, by=) against two projection scans")
+                         "under isin(), aggregate(join=, by=) against two projection scans, and "
+                         "a two-dimension StarJoin aggregate against one join per scan")
     ap.add_argument("--join-pairs", type=int, default=15)
     ap.add_argument("--hashagg", action="store_true",
                     help="add the row GROUP BY HashBy(val), a million distinct keys, alternated "
@@ -778,6 +879,7 @@ def main(argv=None) -> int:
             res["agg"] = agg_rows(path, fd, a, col)
         if a.join:
             res["join"] = join_rows(path, fd, a, col)
+            res["join"]["star"] = star_row(path, fd, a, col)
         if a.hashagg:
             res["hashagg"] = hashagg_row(path, fd, a, col)
         if a.topk:

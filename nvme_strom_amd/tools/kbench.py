@@ -37,6 +37,7 @@ def main(argv=None):
                     help="also: mvcc (snapshot check), par (LZ4 decoders by stream count), "
                          "agg (aggregate kernels next to column_filter_i64), "
                          "join (hash-join probe next to column_filter_i64), "
+                         "join_star (star probe of 2-4 legs next to the chained probes), "
                          "hashagg (hash GROUP BY next to column_filter_i64 and the LDS path), "
                          "topk (ORDER BY ... LIMIT k select + merge next to column_filter_i64)")
     ap.add_argument("--out", default="")
@@ -186,6 +187,8 @@ def main(argv=None):
         _agg_rows(n, dev, log, column_filter)
     if "join" in only:
         _join_rows(n, dev, log, column_filter)
+    if "join_star" in only:
+        _join_star_rows(n, dev, log, column_filter)
     if "hashagg" in only:
         _hashagg_rows(n, dev, log, column_filter)
     if "topk" in only:
@@ -278,6 +281,62 @@ def _join_rows(n, dev, log, column_filter):
         print(f"column_join table {tag}: {nk} keys, largest displacement {int(hdr[J.H_MAXDISP])}",
               file=sys.stderr, flush=True)
         del fk, table
+
+
+def _join_star_rows(n, dev, log, column_filter):
+    """The star probe (strom_column_join_star: 2, 3 and 4 legs in one walk of
+    the bitmap) next to the same legs as a chain of strom_column_join launches,
+    the first from the source bitmap and the rest in place, over the same
+    inputs in the same run: fk columns int64, int32, int64, int32 on one
+    HBM-resident record batch, each leg with a table of its own that keeps
+    about half of what reaches it; tables of 64 KiB and 64 MiB each; 100 % and
+    1 % (random) source selection.  GB/s of the legs' fk bytes.  The two
+    results are compared before they are timed."""
+    from nvme_strom_amd.ops import coljoin as J
+    nv = n // 8
+    nwords = (nv + 63) // 64
+    v = torch.randint(-1000, 1000, (nv,), dtype=torch.int64, device=dev)
+    log("column_filter_i64", timed(lambda: column_filter(v, -100, 100), 20), nv * 8)
+    sels = {"100": torch.full((nwords,), -1, dtype=torch.int64, device=dev),
+            "1": column_filter(v, -10, 9)[0]}
+    del v
+    dst = torch.empty(nwords, dtype=torch.int64, device=dev)
+    dst2 = torch.empty(nwords, dtype=torch.int64, device=dev)
+    cnt = torch.zeros(3, dtype=torch.int64, device=dev)
+    kinds = [("i8", torch.int64), ("i4", torch.int32)] * 2
+    for tag, nbytes in (("64KiB", 64 << 10), ("64MiB", 64 << 20)):
+        nk = nbytes // 32                       # 16-byte slots, capacity = 2n
+        tables, fks = [], []
+        for i, (st, dt) in enumerate(kinds):
+            # every leg its own keys: the odd or the even numbers, shifted
+            keys = torch.arange(nk, dtype=torch.int64, device=dev) * 2 + (i & 1)
+            tables.append(J.build(keys, None))
+            fks.append(torch.randint(0, 2 * nk, (nv,), dtype=dt, device=dev))
+            del keys
+        tabs = torch.tensor([[[f.data_ptr(), 0, nv, 0, 0]] for f in fks], dtype=torch.int64,
+                            device=dev)
+        for nl in (2, 3, 4):
+            legs = [(tables[i], J.FK_CODE[kinds[i][0]], J.SEMI, -1) for i in range(nl)]
+            nb = sum(f.element_size() for f in fks[:nl]) * nv
+            for sel, bm in sels.items():
+                def chain():
+                    for i in range(nl):
+                        # only the last launch's count is the chain's
+                        J.probe(tables[i], legs[i][1], tabs[i], nwords, bm if i == 0 else dst, dst,
+                                cnt[:1] if i == nl - 1 else cnt[2:])
+
+                def star():
+                    J.probe_star(legs, tabs[:nl], nwords, bm, dst2, cnt[1:2])
+                cnt.zero_()
+                chain()
+                star()
+                both = cnt.tolist()
+                if both[0] != both[1] or not torch.equal(dst, dst2):
+                    raise RuntimeError(f"join_star {nl} legs, table {tag}, sel {sel}: the star "
+                                       f"kept {both[1]} rows, the chain {both[0]}")
+                log(f"join_chain_{nl}legs_table{tag}_sel{sel}", timed(chain, 20), nb)
+                log(f"join_star_{nl}legs_table{tag}_sel{sel}", timed(star, 20), nb)
+        del tables, fks, tabs
 
 
 def _topk_rows(n, dev, log, column_filter):

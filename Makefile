@@ -158,6 +158,15 @@ build/coltopk_fuzz: csrc/tests/coltopk_fuzz.cc csrc/kernels/coltopk.hip csrc/inc
 	  -Xarch_host -fno-sanitize-recover=all -fno-omit-frame-pointer \
 	  -o $@ csrc/tests/coltopk_fuzz.cc csrc/kernels/coltopk.hip
 
+# the heap scan's host copy (page checks, deformer, qualifier evaluators,
+# snapshot check, projection), host-only with ASan + UBSan
+build/heapscan_fuzz: csrc/tests/heapscan_fuzz.cc csrc/kernels/heapscan.hip csrc/include/strom/strom.h
+	@mkdir -p build
+	$(HIPCC) -std=c++17 -O1 -g -Icsrc/include --offload-arch=$(ARCH) \
+	  -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
+	  -Xarch_host -fno-sanitize-recover=all -fno-omit-frame-pointer \
+	  -o $@ csrc/tests/heapscan_fuzz.cc csrc/kernels/heapscan.hip
+
 selftest: build/selftest build/selftest-asan build/selftest-tsan
 	STROM_STAT_SHM=0 ./build/selftest && STROM_STAT_SHM=0 ./build/selftest-asan && STROM_STAT_SHM=0 TSAN_OPTIONS=report_signal_unsafe=0 ./build/selftest-tsan
 

@@ -413,6 +413,38 @@ int strom_heap_project_n(const void *pages, uint32_t page_sz, const uint32_t *it
                          const struct strom_heap_tupdesc *desc, const int32_t *attnos,
                          uint32_t ncol, uint64_t float_mask, uint64_t *values, uint8_t *valid,
                          void *stream);
+/* What the heap scan and the projection take for a tuple, in one place (the
+ * kernels, their host copy and the Python models in utils/pgpage.py and
+ * utils/pgtuple.py follow it; docs/ARCHITECTURE.md, "Malformed heap input"):
+ * a line pointer is followed when it is LP_NORMAL, lp_len >= 23, lp_off >= 24,
+ * lp_off + lp_len <= page_sz and lp_off is MAXALIGNed (lp_off & 7 == 0, as
+ * PageAddItem writes it; the aligned readers rely on it).  Every read of a
+ * tuple is bounds-checked against lp_len first and wide reads touch only the
+ * aligned 4-byte words that hold a byte of the datum, so nothing past
+ * `pages + npages * page_sz` is read: `pages` needs no slack, only 4-byte
+ * alignment of its start.
+ *
+ * The host copy of the scan kernels: the same per-tuple code (page header
+ * checks, checksum, deformer, qualifier evaluators, snapshot check) run over
+ * the pages in order, one tuple at a time.  Every pointer of *g — pages,
+ * outputs, prog / cpool, the mvcc lists — is HOST memory; out_items comes out
+ * ascending.  gen selects the evaluator: 0 the fixed-offset int predicate of
+ * strom_heap_scan (base.attr_off / lo / hi; desc and quals unused), 1 the
+ * fixed AND list (prog must be NULL), 2 the program (prog != NULL, checked
+ * here with strom_heap_prog_check).  Argument checks are those of the device
+ * entries; recheck_count / mvcc_removed are added to, as on the device. */
+int strom_heap_scan2_host(const struct strom_heap_scan2_args *g, int gen);
+/* strom_heap_project_n on host memory (*count items, at most cap read) */
+int strom_heap_project_host(const void *pages, uint32_t page_sz, const uint32_t *items,
+                            const uint32_t *count, uint32_t cap,
+                            const struct strom_heap_tupdesc *desc, const int32_t *attnos,
+                            uint32_t ncol, uint64_t float_mask, uint64_t *values, uint8_t *valid);
+/* The scan's launch shape for npages pages of page_sz bytes: workgroups, and
+ * pages per wave per output reservation (a workgroup of 4 waves takes
+ * 4 * pages_per_wave pages per trip of its grid-stride loop).  The launch
+ * itself calls this.  0 or -EINVAL. */
+int strom_heap_scan_geometry(uint32_t page_sz, uint32_t npages, uint32_t *grid,
+                             uint32_t *pages_per_wave);
 uint16_t strom_pg_checksum_host(const void *page, uint32_t blkno,
                                 uint32_t page_sz);
 /* Per-tuple MVCC check of a heap page against a snapshot (xmin, xmax,

@@ -34,22 +34,42 @@
 // prefix).  Quals are sorted by attribute, so one walk per tuple serves them
 // all.  strom_heap_project gathers one attribute of the selected tuples with
 // the same deformer, reading the pages in HBM.
+//
+// The per-tuple code — header checks, the deformer, the qualifier evaluators
+// and the snapshot check — is host-device text: the kernels run it per lane,
+// strom_heap_scan2_host / strom_heap_project_host run the same functions in
+// a loop over pages and tuples (the hand-built corpus and the sanitizer fuzz
+// go through those, tests/heapcorpus.py, csrc/tests/heapscan_fuzz.cc).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <cstring>
 
 #include "strom/strom.h"
+
+#define HD __host__ __device__ __forceinline__
+// the constant address space exists on the device only
+#if defined(__HIP_DEVICE_COMPILE__)
+#define STROM_CONST_AS __attribute__((address_space(4)))
+#else
+#define STROM_CONST_AS
+#endif
 
 namespace {
 
 // pg_checksum's per-lane FNV offsets (checksum_impl.h, checksumBaseOffsets)
-__constant__ uint32_t g_pg_base[32] = {
-    0x5B1F36E9, 0xB8525960, 0x02AB50AA, 0x1DE66D2A, 0x79FF467A, 0x9BB9F8A3, 0x217E7CD2,
-    0x83E13D2C, 0xF8D4474F, 0xE39EB970, 0x42C6AE16, 0x993216FA, 0x7B093B5D, 0x98DAFF3C,
-    0xF718902A, 0x0B1C9CDB, 0xE58F764B, 0x187636BC, 0x5D7B3BB1, 0xE73DE7DE, 0x92BEC979,
-    0xCCA6C0B2, 0x304A0979, 0x85AA43D4, 0x783125BB, 0x6CA8EAA2, 0xE407EAC6, 0x4B5CFC3E,
-    0x9FBF8C76, 0x15CA20BE, 0xF2CA9FFF, 0x3ED50F2B};
+#define STROM_PG_BASE_OFFSETS \
+  0x5B1F36E9, 0xB8525960, 0x02AB50AA, 0x1DE66D2A, 0x79FF467A, 0x9BB9F8A3, 0x217E7CD2, \
+  0x83E13D2C, 0xF8D4474F, 0xE39EB970, 0x42C6AE16, 0x993216FA, 0x7B093B5D, 0x98DAFF3C, \
+  0xF718902A, 0x0B1C9CDB, 0xE58F764B, 0x187636BC, 0x5D7B3BB1, 0xE73DE7DE, 0x92BEC979, \
+  0xCCA6C0B2, 0x304A0979, 0x85AA43D4, 0x783125BB, 0x6CA8EAA2, 0xE407EAC6, 0x4B5CFC3E, \
+  0x9FBF8C76, 0x15CA20BE, 0xF2CA9FFF, 0x3ED50F2B
+__constant__ __attribute__((unused)) uint32_t g_pg_base[32] = {STROM_PG_BASE_OFFSETS};
+#if !defined(__HIP_DEVICE_COMPILE__)
+const uint32_t g_pg_base_host[32] = {STROM_PG_BASE_OFFSETS};   // the host copy reads this one
+#endif
 
 constexpr uint32_t kSizeOfPageHeader = 24;
 constexpr uint32_t kLpNormal = 1;
@@ -61,7 +81,7 @@ constexpr uint32_t kPdAllVisible = 0x0004;
 constexpr int kWaves = 4;
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ uint32_t fnv_mix(uint32_t s, uint32_t v) {
+HD uint32_t fnv_mix(uint32_t s, uint32_t v) {
   uint32_t t = s ^ v;
   return t * 16777619u ^ (t >> 17);
 }
@@ -69,10 +89,10 @@ __device__ __forceinline__ uint32_t fnv_mix(uint32_t s, uint32_t v) {
 // little-endian reads from the LDS page image.  Tuple offsets are MAXALIGNed
 // but user columns need not be 4-aligned, so wide reads are assembled from
 // the two aligned words around them.
-__device__ __forceinline__ uint32_t lds_u32a(const uint8_t *pg, uint32_t off) {
+HD uint32_t lds_u32a(const uint8_t *pg, uint32_t off) {
   return *(const uint32_t *)(pg + off);  // off % 4 == 0
 }
-__device__ __forceinline__ uint32_t lds_u32(const uint8_t *pg, uint32_t off) {
+HD uint32_t lds_u32(const uint8_t *pg, uint32_t off) {
   const uint32_t sh = (off & 3) * 8;
   const uint32_t lo = lds_u32a(pg, off & ~3u);
   if (!sh) return lo;
@@ -84,7 +104,7 @@ struct PageHdr {
   uint32_t checksum, flags, lower, upper, special, psv;
 };
 
-__device__ __forceinline__ PageHdr read_hdr(const uint8_t *pg) {
+HD PageHdr read_hdr(const uint8_t *pg) {
   PageHdr h;
   const uint32_t w2 = lds_u32a(pg, 8), w3 = lds_u32a(pg, 12), w4 = lds_u32a(pg, 16);
   h.checksum = w2 & 0xffff;
@@ -96,21 +116,11 @@ __device__ __forceinline__ PageHdr read_hdr(const uint8_t *pg) {
   return h;
 }
 
-// page header check + optional checksum; returns STROM_PAGE_* bits
-__device__ uint32_t page_status(const strom_heap_scan_args &a, const uint8_t *pg,
-                                const PageHdr &h, uint32_t page_no, uint32_t lane) {
-  if (h.upper == 0) return STROM_PAGE_EMPTY;
-  if (h.lower < kSizeOfPageHeader || h.lower > h.upper || h.upper > h.special ||
-      h.special > a.page_sz || (h.special & 7) || (h.flags & ~0x7u) ||
-      (h.psv & 0xFF00u) != (a.page_sz & 0xFF00u))
-    return STROM_PAGE_BAD_HEADER;
-  if (!(a.flags & STROM_HEAP_VERIFY_CHECKSUM)) return 0;
-  // lanes 0..31 own one FNV sum each (lanes 32..63 duplicate and are
-  // ignored); lane j reads column j of each 128-B row: 32 consecutive words
-  const uint32_t j = lane & 31;
+// one of pg_checksum_page's 32 interleaved FNV-1a sums: column j of each
+// 128-B row (32 consecutive words), two rounds of zeroes at the end
+HD uint32_t fnv_column(const uint8_t *pg, uint32_t page_sz, uint32_t j, uint32_t s) {
   const uint32_t *w = (const uint32_t *)pg;
-  uint32_t s = g_pg_base[j];
-  const uint32_t rows = a.page_sz / 128;
+  const uint32_t rows = page_sz / 128;
   {
     uint32_t v = w[j];
     if (j == 2) v &= 0xffff0000u;  // pd_checksum reads as zero
@@ -119,21 +129,42 @@ __device__ uint32_t page_status(const strom_heap_scan_args &a, const uint8_t *pg
   for (uint32_t r = 1; r < rows; ++r) s = fnv_mix(s, w[r * 32 + j]);
   s = fnv_mix(s, 0);
   s = fnv_mix(s, 0);
+  return s;
+}
+
+// page header check + optional checksum; returns STROM_PAGE_* bits
+__host__ __device__ uint32_t page_status(const strom_heap_scan_args &a, const uint8_t *pg,
+                                const PageHdr &h, uint32_t page_no, uint32_t lane) {
+  if (h.upper == 0) return STROM_PAGE_EMPTY;
+  if (h.lower < kSizeOfPageHeader || h.lower > h.upper || h.upper > h.special ||
+      h.special > a.page_sz || (h.special & 7) || (h.flags & ~0x7u) ||
+      (h.psv & 0xFF00u) != (a.page_sz & 0xFF00u))
+    return STROM_PAGE_BAD_HEADER;
+  if (!(a.flags & STROM_HEAP_VERIFY_CHECKSUM)) return 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+  // lanes 0..31 own one FNV sum each (lanes 32..63 duplicate and are
+  // ignored); lane j reads column j of each 128-B row: 32 consecutive words
+  const uint32_t j = lane & 31;
+  uint32_t s = fnv_column(pg, a.page_sz, j, g_pg_base[j]);
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) s ^= __shfl_xor(s, o, 64);
+#else
+  uint32_t s = 0;                  // the host copy: the 32 sums one after the other
+  for (uint32_t j = 0; j < 32; ++j) s ^= fnv_column(pg, a.page_sz, j, g_pg_base_host[j]);
+#endif
   const uint32_t blkno = a.blknos ? a.blknos[page_no] : a.blkno_base + page_no;
   const uint32_t c = ((s ^ blkno) % 65535u) + 1u;
   return (c & 0xffffu) != h.checksum ? STROM_PAGE_BAD_CHECKSUM : 0u;
 }
 
 // ---------------------------------------------------------------- deformer
-__device__ __forceinline__ uint32_t align_up(uint32_t off, uint32_t al) {
+HD uint32_t align_up(uint32_t off, uint32_t al) {
   return (off + al - 1) & ~(al - 1);
 }
 
 // TOAST pointer payload size by vartag (postgres.h VARTAG_SIZE): indirect
 // and expanded pointers are 8 bytes, an on-disk varatt_external 16
-__device__ __forceinline__ uint32_t vartag_size(uint32_t tag) {
+HD uint32_t vartag_size(uint32_t tag) {
   return tag == 18 ? 16u : (tag >= 1 && tag <= 3) ? 8u : 0u;
 }
 
@@ -152,7 +183,7 @@ struct Att {
   bool null, ext;               // ext: compressed or out-of-line varlena
 };
 
-__device__ __forceinline__ Deform deform_init(const uint8_t *t, uint32_t tlen) {
+HD Deform deform_init(const uint8_t *t, uint32_t tlen) {
   Deform s;
   s.t = t;
   s.tlen = tlen;
@@ -160,13 +191,16 @@ __device__ __forceinline__ Deform deform_init(const uint8_t *t, uint32_t tlen) {
   s.natts = (w16 >> 16) & 0x7ff;
   s.hasnull = (w20 & kHeapHasNull) != 0;
   s.hoff = (w20 >> 16) & 0xff;
-  s.bad = s.hoff < 23 || s.hoff > tlen || (s.hasnull && 23 + ((s.natts + 7) >> 3) > s.hoff);
+  // t_hoff is MAXALIGNed (heap_form_tuple) and attributes are placed relative
+  // to it: any other value would put the attcacheoff path and the walk apart
+  s.bad = s.hoff < 24 || (s.hoff & 7) || s.hoff > tlen ||
+          (s.hasnull && 23 + ((s.natts + 7) >> 3) > s.hoff);
   s.next = 0;
   s.off = s.hoff;
   return s;
 }
 
-__device__ __forceinline__ Att deform_to(const strom_heap_tupdesc &d, Deform &s, uint32_t k) {
+HD Att deform_to(const strom_heap_tupdesc &d, Deform &s, uint32_t k) {
   Att a;
   a.off = a.len = a.hdr = 0;
   a.null = true;
@@ -237,7 +271,7 @@ __device__ __forceinline__ Att deform_to(const strom_heap_tupdesc &d, Deform &s,
   return a;
 }
 
-__device__ __forceinline__ int64_t att_int(const uint8_t *t, const Att &a) {
+HD int64_t att_int(const uint8_t *t, const Att &a) {
   switch (a.len) {
     case 1: return (int8_t)t[a.off];
     case 2: return (int16_t)(t[a.off] | (t[a.off + 1] << 8));
@@ -246,20 +280,56 @@ __device__ __forceinline__ int64_t att_int(const uint8_t *t, const Att &a) {
   }
 }
 
-__device__ __forceinline__ double att_float(const uint8_t *t, const Att &a) {
-  if (a.len == 4) return (double)__uint_as_float(lds_u32(t, a.off));
-  return __longlong_as_double((long long)att_int(t, a));
+// bit casts: the device's intrinsics, memcpy in the host copy
+HD float bits_f32(uint32_t u) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __uint_as_float(u);
+#else
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+#endif
+}
+HD double bits_f64(int64_t i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __longlong_as_double((long long)i);
+#else
+  double d;
+  memcpy(&d, &i, 8);
+  return d;
+#endif
+}
+HD int64_t f64_bits(double d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (int64_t)__double_as_longlong(d);
+#else
+  int64_t i;
+  memcpy(&i, &d, 8);
+  return i;
+#endif
+}
+
+HD double att_float(const uint8_t *t, const Att &a) {
+  if (a.len == 4) return (double)bits_f32(lds_u32(t, a.off));
+  return bits_f64(att_int(t, a));
 }
 
 // PostgreSQL float ordering: NaN equals NaN and sorts above every number
-__device__ __forceinline__ bool pg_le(double x, double y) {
-  if (isnan(y)) return true;
-  if (isnan(x)) return false;
+HD bool is_nan(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return isnan(x);
+#else
+  return std::isnan(x);
+#endif
+}
+HD bool pg_le(double x, double y) {
+  if (is_nan(y)) return true;
+  if (is_nan(x)) return false;
   return x <= y;
 }
 
 // 1 keep, 0 drop, 2 undecidable here (text qual on a compressed / TOAST value)
-__device__ __forceinline__ int eval_quals(const strom_heap_scan2_args &g, const uint8_t *t,
+HD int eval_quals(const strom_heap_scan2_args &g, const uint8_t *t,
                                           uint32_t tlen) {
   Deform s = deform_init(t, tlen);
   Att a;
@@ -298,7 +368,7 @@ __device__ __forceinline__ int eval_quals(const strom_heap_scan2_args &g, const 
       }
       case STROM_QUAL_FLOAT_RANGE: {
         const double v = att_float(t, a);
-        if (!pg_le(__longlong_as_double(q.lo), v) || !pg_le(v, __longlong_as_double(q.hi))) return 0;
+        if (!pg_le(bits_f64(q.lo), v) || !pg_le(v, bits_f64(q.hi))) return 0;
         break;
       }
       case STROM_QUAL_TEXT_EQ:
@@ -329,12 +399,12 @@ __device__ __forceinline__ int eval_quals(const strom_heap_scan2_args &g, const 
 // The pool through the constant address space (never written while the
 // kernel runs): wave-uniform dword reads are scalar loads.  Every constant
 // starts 8-aligned and the pool is padded to 8 bytes (ops/heapscan.Program).
-typedef const __attribute__((address_space(4))) uint8_t cu8;
-typedef const __attribute__((address_space(4))) uint32_t cu32;
-__device__ __forceinline__ uint32_t pool_u32(cu8 *p, uint32_t o) {   // o % 4 == 0
+typedef const STROM_CONST_AS uint8_t cu8;
+typedef const STROM_CONST_AS uint32_t cu32;
+HD uint32_t pool_u32(cu8 *p, uint32_t o) {   // o % 4 == 0
   return *(cu32 *)(p + o);
 }
-__device__ __forceinline__ uint32_t pool_u16(cu8 *p, uint32_t o) {   // o % 2 == 0
+HD uint32_t pool_u16(cu8 *p, uint32_t o) {   // o % 2 == 0
   return (pool_u32(p, o & ~3u) >> ((o & 2) * 8)) & 0xffff;
 }
 
@@ -348,7 +418,7 @@ struct Num {
   const uint8_t *dig;  // int16 little-endian base-10000 digits
 };
 
-__device__ __forceinline__ bool num_of_datum(const uint8_t *t, const Att &a, Num &n) {
+HD bool num_of_datum(const uint8_t *t, const Att &a, Num &n) {
   const uint32_t len = a.len - a.hdr;
   const uint8_t *d = t + a.off + a.hdr;
   if (len < 2) return false;
@@ -376,7 +446,7 @@ __device__ __forceinline__ bool num_of_datum(const uint8_t *t, const Att &a, Num
   return ((len - 4) & 1) == 0;
 }
 
-__device__ __forceinline__ Num num_of_pool(cu8 *p, uint32_t o) {
+HD Num num_of_pool(cu8 *p, uint32_t o) {
   Num n;
   n.kind = pool_u16(p, o);
   n.neg = pool_u16(p, o + 2);
@@ -386,12 +456,12 @@ __device__ __forceinline__ Num num_of_pool(cu8 *p, uint32_t o) {
   return n;
 }
 
-__device__ __forceinline__ int32_t num_digit(const Num &n, uint32_t i) {
+HD int32_t num_digit(const Num &n, uint32_t i) {
   return (int16_t)((uint32_t)n.dig[2 * i] | ((uint32_t)n.dig[2 * i + 1] << 8));
 }
 
 // cmp_abs_common (numeric.c): |a| vs |b|
-__device__ __forceinline__ int num_cmp_abs(const Num &a, const Num &b) {
+HD int num_cmp_abs(const Num &a, const Num &b) {
   uint32_t i1 = 0, i2 = 0;
   int32_t w1 = a.weight, w2 = b.weight;
   while (w1 > w2 && i1 < a.nd) {
@@ -415,7 +485,7 @@ __device__ __forceinline__ int num_cmp_abs(const Num &a, const Num &b) {
   return 0;
 }
 
-__device__ __forceinline__ bool num_zero(const Num &n) {
+HD bool num_zero(const Num &n) {
   for (uint32_t i = 0; i < n.nd; ++i)
     if (num_digit(n, i)) return false;
   return true;
@@ -423,7 +493,7 @@ __device__ __forceinline__ bool num_zero(const Num &n) {
 
 // cmp_numerics: NaN equals NaN and sorts above everything, +inf above every
 // finite value, -inf below; finite values by sign, then magnitude
-__device__ __forceinline__ int num_cmp(const Num &a, const Num &b) {
+HD int num_cmp(const Num &a, const Num &b) {
   auto rank = [](const Num &n) { return n.kind == 1 ? 3 : n.kind == 2 ? 2 : n.kind == 3 ? 0 : 1; };
   const int ra = rank(a), rb = rank(b);
   if (ra != rb) return ra < rb ? -1 : 1;
@@ -440,7 +510,7 @@ __device__ __forceinline__ int num_cmp(const Num &a, const Num &b) {
 }
 
 // n bytes of a tuple vs a pool constant (8-aligned, read a dword at a time)
-__device__ __forceinline__ bool bytes_eq(const uint8_t *x, cu8 *y, uint32_t n) {
+HD bool bytes_eq(const uint8_t *x, cu8 *y, uint32_t n) {
   for (uint32_t k = 0; k < n; k += 4) {
     const uint32_t w = *(cu32 *)(y + k);
     const uint32_t m = n - k;
@@ -451,7 +521,7 @@ __device__ __forceinline__ bool bytes_eq(const uint8_t *x, cu8 *y, uint32_t n) {
 }
 
 // one qual of a program on attribute a: 1 true, 0 false, 2 undecidable
-__device__ __forceinline__ int eval_qual2(const strom_heap_qual2 &q, cu8 *pool,
+HD int eval_qual2(const strom_heap_qual2 &q, cu8 *pool,
                                           const uint8_t *t, const Att &a) {
   if (q.flags & STROM_QUAL2_FALSE) return 0;
   if (q.kind == STROM_QUAL_IS_NULL) return a.null ? 1 : 0;
@@ -474,7 +544,7 @@ __device__ __forceinline__ int eval_qual2(const strom_heap_qual2 &q, cu8 *pool,
     }
     case STROM_QUAL_FLOAT_RANGE: {
       const double v = att_float(t, a);
-      return pg_le(__longlong_as_double(q.lo), v) && pg_le(v, __longlong_as_double(q.hi));
+      return pg_le(bits_f64(q.lo), v) && pg_le(v, bits_f64(q.hi));
     }
     case STROM_QUAL_TEXT_EQ:
     case STROM_QUAL_TEXT_PREFIX:
@@ -514,7 +584,7 @@ __device__ __forceinline__ int eval_qual2(const strom_heap_qual2 &q, cu8 *pool,
 // evaluating; the wave leaves when every lane has decided), and the program
 // is read through the constant address space, so its entries are scalar
 // loads (profiles/r5/heap/prog_kbench.md)
-__device__ __forceinline__ int eval_prog(const strom_heap_scan2_args &g, const uint8_t *t,
+HD int eval_prog(const strom_heap_scan2_args &g, const uint8_t *t,
                                          uint32_t tlen) {
   Deform s = deform_init(t, tlen);
   Att a;
@@ -530,12 +600,23 @@ __device__ __forceinline__ int eval_prog(const strom_heap_scan2_args &g, const u
   // loads).  One 32-byte s_load per qual, the next one issued before the
   // current qual is evaluated.
   typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
-  typedef const __attribute__((address_space(4))) u32x8 cq8;
+  typedef const STROM_CONST_AS u32x8 cq8;
   static_assert(sizeof(strom_heap_qual2) == 32, "one s_load_dwordx8 per qual");
   cq8 *prog = (cq8 *)g.prog;
   const uint32_t n = g.nprog;
   uint32_t qi = 0;
-  u32x8 w = prog[0];                            // n >= 1 (program mode)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define STROM_HS_QUAL(i) prog[i]
+#else
+  // the host copy: a program in host memory is 8-aligned, not 32
+  auto host_qual = [&](uint32_t i) {
+    u32x8 v;
+    memcpy(&v, (const uint8_t *)prog + 32 * (size_t)i, 32);
+    return v;
+  };
+#define STROM_HS_QUAL(i) host_qual(i)
+#endif
+  u32x8 w = STROM_HS_QUAL(0);                   // n >= 1 (program mode)
   while (qi < n) {
     const uint32_t cl = w[1];
     int cv = 0;                                 // the clause: 0 false, 1 true, 2 unknown
@@ -549,7 +630,7 @@ __device__ __forceinline__ int eval_prog(const strom_heap_scan2_args &g, const u
       q.coff = w[3];
       q.lo = (int64_t)((uint64_t)w[4] | ((uint64_t)w[5] << 32));
       q.hi = (int64_t)((uint64_t)w[6] | ((uint64_t)w[7] << 32));
-      if (++qi < n) w = prog[qi];
+      if (++qi < n) w = STROM_HS_QUAL(qi);
       if (!live || cv == 1) continue;           // decided: skip the clause's rest
       if (q.attno != last) {
         if ((uint32_t)q.attno < s.next) s = deform_init(t, tlen);   // walk again from the start
@@ -573,8 +654,13 @@ __device__ __forceinline__ int eval_prog(const strom_heap_scan2_args &g, const u
         verdict = 2;
       }
     }
+#if defined(__HIP_DEVICE_COMPILE__)
     if (!__ballot(live)) break;                 // every lane decided
+#else
+    if (!live) break;
+#endif
   }
+#undef STROM_HS_QUAL
   return verdict;
 }
 
@@ -599,14 +685,14 @@ struct MvccCtx {
   bool und;
 };
 
-__device__ __forceinline__ bool mv_normal(uint32_t x) { return x >= 3; }
-__device__ __forceinline__ bool mv_precedes(uint32_t a, uint32_t b) {   // TransactionIdPrecedes
+HD bool mv_normal(uint32_t x) { return x >= 3; }
+HD bool mv_precedes(uint32_t a, uint32_t b) {   // TransactionIdPrecedes
   if (!mv_normal(a) || !mv_normal(b)) return a < b;
   return (int32_t)(a - b) < 0;
 }
 
 // membership in an ascending uint32 list (n may be 0)
-__device__ __forceinline__ bool mv_has(const uint32_t *s, uint32_t n, uint32_t x) {
+HD bool mv_has(const uint32_t *s, uint32_t n, uint32_t x) {
   uint32_t lo = 0, hi = n;
   while (lo < hi) {
     const uint32_t mid = (lo + hi) >> 1;
@@ -618,20 +704,20 @@ __device__ __forceinline__ bool mv_has(const uint32_t *s, uint32_t n, uint32_t x
   return false;
 }
 
-__device__ __forceinline__ int mv_clog(MvccCtx &c, uint32_t xid) {   // -1: outside the window
+HD int mv_clog(MvccCtx &c, uint32_t xid) {   // -1: outside the window
   const uint64_t k = (uint32_t)(xid - c.m.clog_base);
   if (!c.m.clog || k >= c.m.clog_n) return -1;
   return (c.m.clog[k >> 2] >> ((k & 3) * 2)) & 3;
 }
 
-__device__ __forceinline__ bool mv_parent(MvccCtx &c, uint32_t xid, uint32_t &p) {
+HD bool mv_parent(MvccCtx &c, uint32_t xid, uint32_t &p) {
   const uint32_t k = xid - c.m.subtrans_base;
   if (!c.m.subtrans || k >= c.m.subtrans_n) return false;
   p = c.m.subtrans[k];
   return true;
 }
 
-__device__ bool mv_did_commit(MvccCtx &c, uint32_t xid) {        // TransactionIdDidCommit
+__host__ __device__ bool mv_did_commit(MvccCtx &c, uint32_t xid) {        // TransactionIdDidCommit
   for (int depth = 0; depth < 1024; ++depth) {
     if (!mv_normal(xid)) return xid == 1 || xid == 2;
     const int st = mv_clog(c, xid);
@@ -653,16 +739,16 @@ __device__ bool mv_did_commit(MvccCtx &c, uint32_t xid) {        // TransactionI
   return false;
 }
 
-__device__ __forceinline__ bool mv_current(MvccCtx &c, uint32_t xid) {
+HD bool mv_current(MvccCtx &c, uint32_t xid) {
   return mv_normal(xid) && mv_has(c.m.curxids, c.m.ncurxids, xid);
 }
 
-__device__ __forceinline__ bool mv_running_bit(const MvccCtx &c, uint32_t xid) {
+HD bool mv_running_bit(const MvccCtx &c, uint32_t xid) {
   const uint32_t k = xid - c.m.xmin;                // xmin <= xid < xmax here
   return (c.run[k >> 5] >> (k & 31)) & 1;
 }
 
-__device__ bool mv_in_snapshot(MvccCtx &c, uint32_t xid) {       // XidInMVCCSnapshot
+__host__ __device__ bool mv_in_snapshot(MvccCtx &c, uint32_t xid) {       // XidInMVCCSnapshot
   if (mv_precedes(xid, c.m.xmin)) return false;
   if (!mv_precedes(xid, c.m.xmax)) return true;
   // the bitmap holds xip (+ subxip when not overflowed) over [xmin, xmax)
@@ -688,14 +774,14 @@ __device__ bool mv_in_snapshot(MvccCtx &c, uint32_t xid) {       // XidInMVCCSna
   return mv_has(c.m.xip, c.m.nxip, xid);
 }
 
-__device__ __forceinline__ bool mv_locked_only(uint32_t mask) {   // HEAP_XMAX_IS_LOCKED_ONLY
+HD bool mv_locked_only(uint32_t mask) {   // HEAP_XMAX_IS_LOCKED_ONLY
   return (mask & kXmaxLockOnly) ||
          (mask & (kXmaxIsMulti | kXmaxKeyshrLock | kXmaxExclLock)) == kXmaxExclLock;
 }
 
 // MultiXactIdGetUpdateXid over PostgreSQL's member page layout (409 groups
 // of 4 status bytes + 4 xids per 8 KiB page); 0 when every member locks
-__device__ uint32_t mv_update_xid(MvccCtx &c, uint32_t multi) {
+__host__ __device__ uint32_t mv_update_xid(MvccCtx &c, uint32_t multi) {
   const uint32_t k = multi - c.m.mx_base;
   if (!c.m.mx_offsets || k >= c.m.mx_n || !c.m.mx_members) {
     c.und = true;
@@ -724,7 +810,7 @@ __device__ uint32_t mv_update_xid(MvccCtx &c, uint32_t multi) {
 }
 
 // the tuple at t (LDS page image), infomask already read
-__device__ int mvcc_visible(const strom_heap_scan2_args &g, const uint8_t *t, uint32_t mask) {
+__host__ __device__ int mvcc_visible(const strom_heap_scan2_args &g, const uint8_t *t, uint32_t mask) {
   const strom_pg_mvcc &m = g.mvcc;
   MvccCtx c{m, g.mvcc_running, g.mvcc_running_bits, false};
   const uint32_t xmin = lds_u32(t, 0), xmax = lds_u32(t, 4);
@@ -794,12 +880,13 @@ __device__ int mvcc_visible(const strom_heap_scan2_args &g, const uint8_t *t, ui
 // Separate instances: the program evaluator's and the snapshot check's
 // registers and code stay out of the others.
 template <int GEN, bool MV>
-__device__ __forceinline__ int tuple_keep(const strom_heap_scan2_args &g, const uint8_t *pg,
+HD int tuple_keep(const strom_heap_scan2_args &g, const uint8_t *pg,
                                           uint32_t lp, bool all_visible, bool check) {
   const strom_heap_scan_args &a = g.base;
   const uint32_t off = lp & 0x7fff, flags = (lp >> 15) & 3, len = lp >> 17;
+  // a tuple starts MAXALIGNed (PageAddItem), which the aligned readers rely on
   if (flags != kLpNormal || len < 23 || off < kSizeOfPageHeader || off + len > a.page_sz ||
-      (off & 1))
+      (off & 7))
     return 0;
   const uint32_t w20 = lds_u32(pg, off + 20);  // t_infomask (16) | t_hoff (8) | bits
   const uint32_t infomask = w20 & 0xffff, hoff = (w20 >> 16) & 0xff;
@@ -959,29 +1046,50 @@ __global__ __launch_bounds__(256) void heap_scan_kernel(strom_heap_scan2_args g,
 #undef STROM_HS_ISSUE
 }
 
-int heap_scan_launch(const strom_heap_scan2_args &g, int gen, void *stream) {
-  const strom_heap_scan_args *a = &g.base;
+// the scan's launch shape (strom_heap_scan_geometry): workgroups, pages per
+// wave per output reservation, line pointer chunks per page, LDS bytes
+struct HeapGeo {
+  uint32_t maxchunks, ppw, grid;
+  size_t lds;
+};
+
+HeapGeo heap_scan_geometry(uint32_t page_sz, uint32_t npages) {
+  HeapGeo geo;
+  geo.maxchunks = ((page_sz - 24) / 4 + 63) / 64;
+  // pages per wave per output reservation: kPerWave, fewer when the page
+  // images leave too little LDS for the masks (32 KiB pages)
+  const size_t budget = 160u * 1024u - (size_t)kWaves * page_sz - (3 * kWaves + kWaves * kPerWave) * 4;
+  geo.ppw = (uint32_t)std::min<size_t>(kPerWave, budget / ((size_t)kWaves * geo.maxchunks * 8));
+  geo.lds = (size_t)kWaves * page_sz + (size_t)kWaves * geo.ppw * geo.maxchunks * 8 +
+            (2 * kWaves + kWaves * geo.ppw) * 4;
+  // enough workgroups to fill 256 CUs at the occupancy LDS allows, then stride
+  const uint32_t per_cu = (uint32_t)(160u * 1024u / ((geo.lds + 1023) & ~(size_t)1023));
+  geo.grid = geo.ppw ? (npages + kWaves * geo.ppw - 1) / (kWaves * geo.ppw) : 0;
+  const uint32_t cap = 256u * (per_cu ? per_cu : 1u) * 2u;
+  if (geo.grid > cap) geo.grid = cap;
+  return geo;
+}
+
+// the argument checks every scan entry shares, device and host
+int heap_scan_args_check(const strom_heap_scan_args *a) {
   if (!a->pages || !a->out_count) return -22;
   if (a->page_sz < 1024 || (a->page_sz & 1023) || a->page_sz > 32768) return -22;
   if (a->attr_off >= 0 && a->attr_width != 4 && a->attr_width != 8) return -22;
   // (page << 16 | lineno) item ids address at most 65535 pages per call
   if (a->out_items && a->npages > 0xffffu) return -34;
+  return 0;
+}
+
+int heap_scan_launch(const strom_heap_scan2_args &g, int gen, void *stream) {
+  const strom_heap_scan_args *a = &g.base;
+  if (const int rc = heap_scan_args_check(a)) return rc;
   if (a->npages == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   (void)hipMemsetAsync(a->out_count, 0, sizeof(uint32_t), st);
-  const uint32_t maxchunks = ((a->page_sz - 24) / 4 + 63) / 64;
-  // pages per wave per output reservation: kPerWave, fewer when the page
-  // images leave too little LDS for the masks (32 KiB pages)
-  const size_t budget = 160u * 1024u - (size_t)kWaves * a->page_sz - (3 * kWaves + kWaves * kPerWave) * 4;
-  uint32_t ppw = (uint32_t)std::min<size_t>(kPerWave, budget / ((size_t)kWaves * maxchunks * 8));
-  if (ppw < 1) return -22;
-  const size_t lds = (size_t)kWaves * a->page_sz + (size_t)kWaves * ppw * maxchunks * 8 +
-                     (2 * kWaves + kWaves * ppw) * 4;
-  // enough workgroups to fill 256 CUs at the occupancy LDS allows, then stride
-  const uint32_t per_cu = (uint32_t)(160u * 1024u / ((lds + 1023) & ~(size_t)1023));
-  uint32_t grid = (a->npages + kWaves * ppw - 1) / (kWaves * ppw);
-  const uint32_t cap = 256u * (per_cu ? per_cu : 1u) * 2u;
-  if (grid > cap) grid = cap;
+  const HeapGeo geo = heap_scan_geometry(a->page_sz, a->npages);
+  if (geo.ppw < 1) return -22;
+  const uint32_t maxchunks = geo.maxchunks, ppw = geo.ppw, grid = geo.grid;
+  const size_t lds = geo.lds;
   auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, g, maxchunks, ppw); };
   const bool mv = g.mvcc_on != 0;
   if (a->page_sz == 8192) {
@@ -1016,49 +1124,95 @@ struct ProjSpec {
   uint8_t att[STROM_HEAP_MAX_ATTS], slot[STROM_HEAP_MAX_ATTS];
 };
 
-// one thread per selected item: deform its tuple once from the page in HBM,
-// every projected attribute on the way
+// one selected item: deform its tuple once from the page (HBM, or host
+// memory in the host copy), every projected attribute on the way.  An item
+// that names no tuple — no such line pointer, or one the scan would not have
+// followed — projects as NULLs and nothing of its page beyond the header and
+// the line pointer is read.
+HD void project_item(const uint8_t *pages, uint32_t page_sz, uint32_t it, uint32_t i, uint32_t cap,
+                     const strom_heap_tupdesc &desc, const ProjSpec &ps, uint64_t *values,
+                     uint8_t *valid) {
+  const uint32_t pg = it >> 16, lineno = it & 0xffff;
+  const uint8_t *page = pages + (uint64_t)pg * page_sz;
+  const uint32_t lower = lds_u32a(page, 12) & 0xffff;
+  bool tup = false;
+  uint32_t off = 0, len = 0;
+  if (lineno >= 1 && kSizeOfPageHeader + 4 * lineno <= lower && lower <= page_sz) {
+    const uint32_t lp = lds_u32a(page, kSizeOfPageHeader + 4 * (lineno - 1));
+    off = lp & 0x7fff;
+    len = lp >> 17;
+    tup = ((lp >> 15) & 3) == kLpNormal && len >= 23 && off >= kSizeOfPageHeader &&
+          off + len <= page_sz && !(off & 7);
+    if (!tup) off = 0;              // the offset may lie outside the page
+  }
+  Deform s = deform_init(page + off, tup ? len : 0);
+  for (uint32_t j = 0; j < ps.n; ++j) {
+    const uint32_t attno = ps.att[j], slot = ps.slot[j];
+    uint64_t v = 0;
+    uint8_t ok = 0;
+    if (tup) {
+      const Att a = deform_to(desc, s, attno);
+      if (!s.bad && !a.null) {
+        if (desc.attlen[attno] < 0) {   // varlena / cstring: where its bytes are
+          v = ((uint64_t)((uint64_t)pg * page_sz + off + a.off + a.hdr) << 32) | (a.len - a.hdr);
+          ok = a.ext ? 2 : 1;
+        } else if ((ps.fmask >> slot) & 1) {
+          v = (uint64_t)f64_bits(att_float(page + off, a));
+          ok = 1;
+        } else {
+          v = (uint64_t)att_int(page + off, a);
+          ok = 1;
+        }
+      }
+    }
+    values[(size_t)slot * cap + i] = v;
+    if (valid) valid[(size_t)slot * cap + i] = ok;
+  }
+}
+
+// one thread per selected item
 __global__ __launch_bounds__(256) void heap_project_kernel(const uint8_t *pages, uint32_t page_sz,
                                                            const uint32_t *items, const uint32_t *d_count,
                                                            uint32_t cap, strom_heap_tupdesc desc,
                                                            ProjSpec ps, uint64_t *values, uint8_t *valid) {
   const uint32_t n = min(*d_count, cap);
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const uint32_t it = items[i], pg = it >> 16, lineno = it & 0xffff;
-    const uint8_t *page = pages + (uint64_t)pg * page_sz;
-    const uint32_t lower = lds_u32a(page, 12) & 0xffff;
-    bool tup = false;
-    uint32_t off = 0, len = 0;
-    if (lineno >= 1 && kSizeOfPageHeader + 4 * lineno <= lower) {
-      const uint32_t lp = lds_u32a(page, kSizeOfPageHeader + 4 * (lineno - 1));
-      off = lp & 0x7fff;
-      len = lp >> 17;
-      tup = len >= 23 && off >= kSizeOfPageHeader && off + len <= page_sz && !(off & 1);
-    }
-    Deform s = deform_init(page + off, tup ? len : 0);
-    for (uint32_t j = 0; j < ps.n; ++j) {
-      const uint32_t attno = ps.att[j], slot = ps.slot[j];
-      uint64_t v = 0;
-      uint8_t ok = 0;
-      if (tup) {
-        const Att a = deform_to(desc, s, attno);
-        if (!s.bad && !a.null) {
-          if (desc.attlen[attno] < 0) {   // varlena / cstring: where its bytes are
-            v = ((uint64_t)((uint64_t)pg * page_sz + off + a.off + a.hdr) << 32) | (a.len - a.hdr);
-            ok = a.ext ? 2 : 1;
-          } else if ((ps.fmask >> slot) & 1) {
-            v = (uint64_t)__double_as_longlong(att_float(page + off, a));
-            ok = 1;
-          } else {
-            v = (uint64_t)att_int(page + off, a);
-            ok = 1;
-          }
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    project_item(pages, page_sz, items[i], i, cap, desc, ps, values, valid);
+}
+
+// the host copy of the scan: the pages in order, one tuple at a time, the
+// kernels' own per-tuple functions; items come out ascending
+template <int GEN, bool MV>
+void heap_scan_host_pages(const strom_heap_scan2_args &g) {
+  const strom_heap_scan_args &a = g.base;
+  uint32_t count = 0, recheck = 0, removed = 0;
+  for (uint32_t pg = 0; pg < a.npages; ++pg) {
+    const uint8_t *mypage = (const uint8_t *)a.pages + (uint64_t)pg * a.page_sz;
+    const PageHdr h = read_hdr(mypage);
+    uint32_t status = page_status(a, mypage, h, pg, 0);
+    if (status == 0) {
+      const bool all_visible = (h.flags & kPdAllVisible) != 0;
+      const bool check = MV && !all_visible && (!g.mvcc_pages || g.mvcc_pages[pg]);
+      const uint32_t nitems = (h.lower - kSizeOfPageHeader) / 4;
+      uint32_t page_recheck = 0;
+      for (uint32_t i = 0; i < nitems; ++i) {
+        const int keep = tuple_keep<GEN, MV>(g, mypage, lds_u32a(mypage, kSizeOfPageHeader + 4 * i),
+                                             all_visible, check);
+        if (keep & 1) {
+          if (a.out_items && count < a.out_cap) a.out_items[count] = (pg << 16) | (i + 1);
+          ++count;
         }
+        if ((GEN || MV) && (keep & 2)) ++page_recheck;
+        if (MV && (keep & 4)) ++removed;
       }
-      values[(size_t)slot * cap + i] = v;
-      if (valid) valid[(size_t)slot * cap + i] = ok;
+      if (page_recheck) status |= STROM_PAGE_RECHECK;
+      recheck += page_recheck;
     }
+    if (a.page_status) a.page_status[pg] = status;
   }
+  *a.out_count = count;
+  if (g.recheck_count) *g.recheck_count += recheck;
+  if (g.mvcc_removed) *g.mvcc_removed += removed;
 }
 
 }  // namespace
@@ -1166,7 +1320,10 @@ extern "C" int strom_heap_prog_check(const strom_heap_tupdesc *d, const strom_he
   return 0;
 }
 
-extern "C" int strom_heap_scan2(const strom_heap_scan2_args *g, void *stream) {
+// strom_heap_scan2's argument checks, shared with the host copy: 2 (program
+// mode), 1 (the fixed AND list), or a negative errno.  A program was checked
+// by the caller against its host copy (strom_heap_prog_check)
+static int heap_scan2_check(const strom_heap_scan2_args *g) {
   if (!g || g->base.attr_off >= 0) return -22;
   if (g->mvcc_on && mvcc_check(g->mvcc, g->mvcc_running ? g->mvcc_running_bits : 0)) return -22;
   if (g->desc.natts < 1 || g->desc.natts > STROM_HEAP_MAX_ATTS) return -22;
@@ -1174,11 +1331,9 @@ extern "C" int strom_heap_scan2(const strom_heap_scan2_args *g, void *stream) {
     const int al = g->desc.attalign[i], len = g->desc.attlen[i];
     if ((al != 1 && al != 2 && al != 4 && al != 8) || len == 0 || len < -2) return -22;
   }
-  // a program was checked by the caller against its host copy
-  // (strom_heap_prog_check); it lives in device memory here
   if (g->prog) {
     if (!g->nprog || !g->cpool || (g->cpool_len & 7)) return -22;   // the kernel reads prog[0]
-    return heap_scan_launch(*g, 2, stream);
+    return 2;
   }
   if (g->nquals < 0 || g->nquals > STROM_HEAP_MAX_QUALS) return -22;
   int last = -1;
@@ -1207,19 +1362,66 @@ extern "C" int strom_heap_scan2(const strom_heap_scan2_args *g, void *stream) {
         return -22;
     }
   }
-  return heap_scan_launch(*g, 1, stream);
+  return 1;
 }
 
-extern "C" int strom_heap_project_n(const void *pages, uint32_t page_sz, const uint32_t *items,
-                                    const uint32_t *d_count, uint32_t cap,
-                                    const strom_heap_tupdesc *desc, const int32_t *attnos,
-                                    uint32_t ncol, uint64_t float_mask, uint64_t *values,
-                                    uint8_t *valid, void *stream) {
-  if (!pages || !items || !d_count || !desc || !values || !attnos) return -22;
+extern "C" int strom_heap_scan2(const strom_heap_scan2_args *g, void *stream) {
+  const int gen = heap_scan2_check(g);
+  if (gen < 0) return gen;
+  return heap_scan_launch(*g, gen, stream);
+}
+
+extern "C" int strom_heap_scan_geometry(uint32_t page_sz, uint32_t npages, uint32_t *grid,
+                                        uint32_t *pages_per_wave) {
+  if (page_sz < 1024 || (page_sz & 1023) || page_sz > 32768) return -22;
+  const HeapGeo geo = heap_scan_geometry(page_sz, npages);
+  if (geo.ppw < 1) return -22;
+  if (grid) *grid = geo.grid;
+  if (pages_per_wave) *pages_per_wave = geo.ppw;
+  return 0;
+}
+
+extern "C" int strom_heap_scan2_host(const strom_heap_scan2_args *g, int gen) {
+  if (!g || gen < 0 || gen > 2) return -22;
+  if (gen == 0) {
+    // strom_heap_scan / strom_heap_scan_mvcc
+    if (g->mvcc_on && mvcc_check(g->mvcc, g->mvcc_running ? g->mvcc_running_bits : 0)) return -22;
+  } else {
+    const int mode = heap_scan2_check(g);
+    if (mode < 0) return mode;
+    if (mode != gen) return -22;
+    if (gen == 2 && strom_heap_prog_check(&g->desc, g->prog, g->nprog, g->cpool, g->cpool_len))
+      return -22;
+  }
+  if (const int rc = heap_scan_args_check(&g->base)) return rc;
+  if (g->base.npages == 0) return 0;
+  *g->base.out_count = 0;
+  const bool mv = g->mvcc_on != 0;
+  if (mv) {
+    if (gen == 2) heap_scan_host_pages<2, true>(*g);
+    else if (gen == 1) heap_scan_host_pages<1, true>(*g);
+    else heap_scan_host_pages<0, true>(*g);
+  } else {
+    if (gen == 2) heap_scan_host_pages<2, false>(*g);
+    else if (gen == 1) heap_scan_host_pages<1, false>(*g);
+    else heap_scan_host_pages<0, false>(*g);
+  }
+  return 0;
+}
+
+// the projection's argument checks and its column list, device and host
+static int heap_project_spec(const void *pages, uint32_t page_sz, const uint32_t *items,
+                             const uint32_t *count, const strom_heap_tupdesc *desc,
+                             const int32_t *attnos, uint32_t ncol, uint64_t float_mask,
+                             const uint64_t *values, ProjSpec &ps) {
+  if (!pages || !items || !count || !desc || !values || !attnos) return -22;
   if (desc->natts < 1 || desc->natts > STROM_HEAP_MAX_ATTS) return -22;
   if (ncol < 1 || ncol > STROM_HEAP_MAX_ATTS) return -22;
   if (page_sz < 1024 || (page_sz & 1023) || page_sz > 32768) return -22;
-  ProjSpec ps;
+  for (int i = 0; i < desc->natts; ++i) {
+    const int al = desc->attalign[i], len = desc->attlen[i];
+    if ((al != 1 && al != 2 && al != 4 && al != 8) || len == 0 || len < -2) return -22;
+  }
   __builtin_memset(&ps, 0, sizeof ps);
   ps.n = ncol;
   ps.fmask = float_mask;
@@ -1228,6 +1430,8 @@ extern "C" int strom_heap_project_n(const void *pages, uint32_t page_sz, const u
     if (k < 0 || k >= desc->natts) return -22;
     const int len = desc->attlen[k];
     if (((float_mask >> j) & 1) && len != 4 && len != 8) return -22;
+    // a fixed-length value is read as 1, 2, 4 or 8 bytes (a longer one: its first 8)
+    if (len > 0 && len < 8 && len != 1 && len != 2 && len != 4) return -22;
     ps.att[j] = (uint8_t)k;
     ps.slot[j] = (uint8_t)j;
   }
@@ -1239,6 +1443,33 @@ extern "C" int strom_heap_project_n(const void *pages, uint32_t page_sz, const u
     }
   for (uint32_t j = 1; j < ncol; ++j)
     if (ps.att[j] == ps.att[j - 1]) return -22;
+  return 0;
+}
+
+extern "C" int strom_heap_project_host(const void *pages, uint32_t page_sz, const uint32_t *items,
+                                       const uint32_t *count, uint32_t cap,
+                                       const strom_heap_tupdesc *desc, const int32_t *attnos,
+                                       uint32_t ncol, uint64_t float_mask, uint64_t *values,
+                                       uint8_t *valid) {
+  ProjSpec ps;
+  if (const int rc = heap_project_spec(pages, page_sz, items, count, desc, attnos, ncol,
+                                       float_mask, values, ps))
+    return rc;
+  const uint32_t n = std::min(*count, cap);
+  for (uint32_t i = 0; i < n; ++i)
+    project_item((const uint8_t *)pages, page_sz, items[i], i, cap, *desc, ps, values, valid);
+  return 0;
+}
+
+extern "C" int strom_heap_project_n(const void *pages, uint32_t page_sz, const uint32_t *items,
+                                    const uint32_t *d_count, uint32_t cap,
+                                    const strom_heap_tupdesc *desc, const int32_t *attnos,
+                                    uint32_t ncol, uint64_t float_mask, uint64_t *values,
+                                    uint8_t *valid, void *stream) {
+  ProjSpec ps;
+  if (const int rc = heap_project_spec(pages, page_sz, items, d_count, desc, attnos, ncol,
+                                       float_mask, values, ps))
+    return rc;
   if (cap == 0) return 0;
   const uint32_t grid = std::min<uint32_t>((cap + 255) / 256, 4096);
   hipLaunchKernelGGL(heap_project_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,

@@ -309,6 +309,12 @@ _SIGS = {
     "strom_heap_project_n": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                        C.POINTER(HeapTupDesc), C.c_void_p, C.c_uint32,
                                        C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "strom_heap_scan2_host": (C.c_int, [C.POINTER(HeapScan2Args), C.c_int]),
+    "strom_heap_project_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_uint32, C.POINTER(HeapTupDesc), C.c_void_p,
+                                          C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "strom_heap_scan_geometry": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_uint32)]),
     "strom_decompress": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                    C.c_void_p, C.c_void_p]),
     "strom_filter_bounds": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),

@@ -23,12 +23,19 @@ PAGE_EMPTY = 4
 @dataclass
 class HeapScanResult:
     items: torch.Tensor        # int32 (page << 16 | lineno), unordered
-    count: int
+    count: int                 # items written: min(total, the items' capacity)
     page_status: torch.Tensor  # int32 per page (PAGE_* bits)
     # snapshot mode (mvcc=): tuples the device check removed; tuples it could
     # not decide (kept, their pages flagged PAGE_RECHECK) add to ``recheck``
     removed: int = 0
     recheck: int = 0
+    # every qualifying tuple the device counted: above ``count`` when
+    # ``out_cap`` cut the item list short
+    total: int = 0
+
+    @property
+    def truncated(self) -> bool:
+        return int(self.total) > int(self.count)
 
     def sorted_items(self) -> np.ndarray:
         return np.sort(self.items[:self.count].cpu().numpy().view(np.uint32))
@@ -142,7 +149,8 @@ def heap_scan(pages: torch.Tensor, page_sz: int = 8192, verify_checksum: bool = 
                                          ptr(cnt) + 4, mvcc.running, mvcc.running_bits,
                                          stream_handle(stream)), "heap_scan_mvcc")
     c = cnt.cpu().tolist()
-    return HeapScanResult(items, min(c[0], cap), status[:npages], removed=c[2], recheck=c[1])
+    return HeapScanResult(items, min(c[0], cap), status[:npages], removed=c[2], recheck=c[1],
+                          total=c[0])
 
 
 # ------------------------------------------------- tuple descriptor + quals
@@ -304,7 +312,11 @@ class Program:
                         if not args[0]:
                             never(k, ci)
                         continue
-                    lo, hi = -math.inf, math.inf
+                    # PostgreSQL's float order: NaN = NaN, above +inf.  A
+                    # bound of NaN passes everything on the upper side and
+                    # only NaN on the lower one (pg_le), so "x >= c" is
+                    # [c, NaN] — NaN rows included — and "x <= c" [-inf, c]
+                    lo, hi = -math.inf, math.nan
                     if op == "between":
                         lo, hi = float(args[0]), float(args[1])
                     elif op == "eq":
@@ -312,11 +324,19 @@ class Program:
                     elif op == "le":
                         hi = float(args[0])
                     elif op == "lt":
-                        hi = math.nextafter(float(args[0]), -math.inf)
+                        c = float(args[0])
+                        if c == -math.inf:            # nothing sorts below -inf
+                            never(k, ci)
+                            continue
+                        hi = math.inf if math.isnan(c) else math.nextafter(c, -math.inf)
                     elif op == "ge":
                         lo = float(args[0])
                     elif op == "gt":
-                        lo = math.nextafter(float(args[0]), math.inf)
+                        c = float(args[0])
+                        if math.isnan(c):             # nothing sorts above NaN
+                            never(k, ci)
+                            continue
+                        lo = math.nan if c == math.inf else math.nextafter(c, math.inf)
                     else:
                         raise ValueError(f"{op} on a float column")
                     emit(k, 2, ci, lo=_fbits(lo), hi=_fbits(hi))
@@ -538,10 +558,12 @@ def heap_scan2(pages: torch.Tensor, desc, quals, page_sz: int = 8192,
         r = HeapScan2Result(items, cnt[0:1], status[:npages])
         r.recheck = cnt[1:2]
         r.removed = cnt[2:3]
+        r.total = cnt[0:1]
         r.keep = keep
         return r
     c = cnt.cpu().tolist()
-    return HeapScan2Result(items, min(c[0], cap), status[:npages], removed=c[2], recheck=c[1])
+    return HeapScan2Result(items, min(c[0], cap), status[:npages], removed=c[2], recheck=c[1],
+                           total=c[0])
 
 
 def heap_project(pages: torch.Tensor, items: torch.Tensor, count: torch.Tensor, desc, col,
@@ -591,3 +613,145 @@ def heap_project_many(pages: torch.Tensor, items: torch.Tensor, count: torch.Ten
         v = vals[j, :n]
         out[c] = (v.view(torch.float64) if (fmask >> j) & 1 else v, valid[j, :n])
     return out
+
+
+# ---------------------------------------------------------------- host copy
+# strom_heap_scan2_host / strom_heap_project_host: the kernels' per-tuple code
+# run on the CPU over bytes and numpy arrays (no torch device).  The tests
+# hold the kernels, these and the Python models against each other.
+@dataclass
+class HostScanResult:
+    items: np.ndarray          # uint32 (page << 16 | lineno), ascending, ``count`` of them
+    count: int
+    total: int
+    page_status: np.ndarray    # uint32 per page
+    removed: int = 0
+    recheck: int = 0
+
+
+def _host_pages(data) -> np.ndarray:
+    a = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else \
+        np.ascontiguousarray(data.view(np.uint8).reshape(-1))
+    if a.ctypes.data & 3:
+        a = np.require(a, requirements=["A", "C"]).copy()
+    return a
+
+
+def _host_run(g, gen: int, pages: np.ndarray, npages: int, page_sz: int, flags: int,
+              blkno_base: int, blknos, out_cap, mvcc, mvcc_pages, base_kw: dict) -> HostScanResult:
+    cap = out_cap if out_cap is not None else npages * (page_sz // 28 + 1)
+    items = np.zeros(max(cap, 1), dtype=np.uint32)
+    cnt = np.zeros(3, dtype=np.uint32)           # count, recheck, removed
+    status = np.zeros(max(npages, 1), dtype=np.uint32)
+    keep = [pages, items, cnt, status]
+    bn = None
+    if blknos is not None:
+        bn = np.ascontiguousarray(np.asarray(blknos, dtype=np.uint32))
+        if bn.size < npages:
+            raise ValueError(f"blknos has {bn.size} entries for {npages} pages")
+    g.base = N.HeapScanArgs(pages=pages.ctypes.data, npages=npages, page_sz=page_sz, flags=flags,
+                            out_items=items.ctypes.data, out_cap=cap, out_count=cnt.ctypes.data,
+                            page_status=status.ctypes.data, blkno_base=blkno_base,
+                            blknos=bn.ctypes.data if bn is not None else None, **base_kw)
+    g.recheck_count = cnt.ctypes.data + 4
+    if mvcc is not None:
+        if mvcc.device.type != "cpu":
+            raise ValueError("the host copy takes a DeviceMvcc(..., device='cpu')")
+        g.mvcc, g.mvcc_on = mvcc.struct, 1
+        if mvcc_pages is not None:
+            mp = np.ascontiguousarray(np.asarray(mvcc_pages, dtype=np.uint8))
+            if mp.size < npages:
+                raise ValueError(f"mvcc_pages has {mp.size} entries for {npages} pages")
+            keep.append(mp)
+            g.mvcc_pages = mp.ctypes.data
+        g.mvcc_removed = cnt.ctypes.data + 8
+        g.mvcc_running, g.mvcc_running_bits = mvcc.running, mvcc.running_bits
+    check(lib().strom_heap_scan2_host(C.byref(g), gen), "heap_scan2_host")
+    total = int(cnt[0])
+    n = min(total, cap)
+    return HostScanResult(items[:n].copy(), n, total, status[:npages].copy(),
+                          removed=int(cnt[2]), recheck=int(cnt[1]))
+
+
+def host_scan_native(data, page_sz: int = 8192, verify_checksum: bool = False,
+                     skip_invisible: bool = False, attr_off: int = -1, attr_width: int = 4,
+                     lo: int = -(1 << 63), hi: int = (1 << 63) - 1, blkno_base: int = 0,
+                     out_cap: Optional[int] = None, blknos=None, mvcc=None,
+                     mvcc_pages=None) -> HostScanResult:
+    """:func:`heap_scan` on the CPU: ``data`` is bytes (or a uint8 array)."""
+    pages = _host_pages(data)
+    if pages.size % page_sz:
+        raise ValueError("pages is not a whole number of pages")
+    flags = (VERIFY_CHECKSUM if verify_checksum else 0) | (SKIP_INVISIBLE if skip_invisible else 0)
+    return _host_run(N.HeapScan2Args(), 0, pages, pages.size // page_sz, page_sz, flags,
+                     blkno_base, blknos, out_cap, mvcc, mvcc_pages,
+                     dict(attr_off=attr_off, attr_width=attr_width, lo=lo, hi=hi))
+
+
+def host_scan2_native(data, desc, quals, page_sz: int = 8192, verify_checksum: bool = False,
+                      skip_invisible: bool = False, blkno_base: int = 0,
+                      out_cap: Optional[int] = None, blknos=None, program: bool = False,
+                      mvcc=None, mvcc_pages=None) -> HostScanResult:
+    """:func:`heap_scan2` on the CPU, choosing the fixed AND list or the
+    program the way heap_scan2 does (``program=True``: always the program)."""
+    pages = _host_pages(data)
+    if pages.size % page_sz:
+        raise ValueError("pages is not a whole number of pages")
+    flags = (VERIFY_CHECKSUM if verify_checksum else 0) | (SKIP_INVISIBLE if skip_invisible else 0)
+    g = N.HeapScan2Args()
+    g.desc = tupdesc_struct(desc)
+    prog = quals if isinstance(quals, Program) else Program(desc, quals)
+    raw, pool = prog.arrays()
+    fx = prog.fixed() if prog.quals and not program else None
+    gen = 1
+    if fx is not None:
+        g.nquals = len(fx)
+        for i, q in enumerate(fx):
+            g.quals[i] = q
+    elif prog.quals:
+        # 8-aligned host copies of the program and its pool
+        hp = np.frombuffer(raw, np.uint8).copy()
+        hc = np.frombuffer(pool, np.uint8).copy()
+        g.prog, g.cpool = hp.ctypes.data, hc.ctypes.data
+        g.nprog, g.cpool_len = len(prog.quals), len(pool)
+        g._keep = (hp, hc)
+        gen = 2
+    return _host_run(g, gen, pages, pages.size // page_sz, page_sz, flags, blkno_base, blknos,
+                     out_cap, mvcc, mvcc_pages, dict(attr_off=-1, attr_width=8, lo=0, hi=0))
+
+
+def host_project_native(data, items, desc, cols, page_sz: int = 8192) -> dict:
+    """:func:`heap_project_many` on the CPU: {column: (values, valid)} of the
+    tuples ``items`` (uint32 item ids) names, numpy arrays."""
+    pages = _host_pages(data)
+    cols = list(cols)
+    ks = [desc.attno(c) for c in cols]
+    it = np.ascontiguousarray(np.asarray(items, dtype=np.uint32))
+    n = int(it.size)
+    m = max(n, 1)
+    if n == 0:
+        it = np.zeros(1, dtype=np.uint32)
+    vals = np.zeros((len(cols), m), dtype=np.int64)
+    valid = np.zeros((len(cols), m), dtype=np.uint8)
+    cnt = np.array([n], dtype=np.uint32)
+    fmask = sum(1 << j for j, k in enumerate(ks) if desc.kinds[k] == "float")
+    att = (C.c_int32 * len(ks))(*ks)
+    d = tupdesc_struct(desc)
+    check(lib().strom_heap_project_host(pages.ctypes.data, page_sz, it.ctypes.data, cnt.ctypes.data,
+                                        m, C.byref(d), C.addressof(att), len(ks), fmask,
+                                        vals.ctypes.data, valid.ctypes.data), "heap_project_host")
+    out = {}
+    for j, c in enumerate(cols):
+        v = vals[j, :n]
+        out[c] = (v.view(np.float64) if (fmask >> j) & 1 else v, valid[j, :n])
+    return out
+
+
+def scan_geometry(page_sz: int, npages: int) -> tuple:
+    """(workgroups, pages per wave per output reservation) of the scan's
+    launch for ``npages`` pages; a workgroup takes 4 x pages-per-wave pages
+    per trip of its grid-stride loop."""
+    grid, ppw = C.c_uint32(0), C.c_uint32(0)
+    check(lib().strom_heap_scan_geometry(page_sz, npages, C.byref(grid), C.byref(ppw)),
+          "heap_scan_geometry")
+    return grid.value, ppw.value

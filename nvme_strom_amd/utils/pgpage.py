@@ -136,11 +136,29 @@ def tuple_visible(infomask: int, pd_flags: int) -> bool:
     return bool(infomask & (HEAP_XMAX_INVALID | HEAP_XMAX_LOCK_ONLY))
 
 
+def line_pointer(page: bytes, lineno: int, page_sz: int = 8192) -> Optional[Tuple[int, int]]:
+    """(lp_off, lp_len) of the tuple line pointer ``lineno`` (1-based) names,
+    or None when it names none: no such pointer below pd_lower, not LP_NORMAL,
+    lp_len < 23, lp_off < 24, lp_off + lp_len > page_sz, or lp_off not
+    MAXALIGNed.  The rule of the scan and of the projection."""
+    lower, = struct.unpack_from("<H", page, 12)
+    if lineno < 1 or 24 + 4 * lineno > lower or lower > page_sz:
+        return None
+    lp, = struct.unpack_from("<I", page, 24 + 4 * (lineno - 1))
+    off, fl, ln = lp & 0x7FFF, (lp >> 15) & 3, lp >> 17
+    if fl != LP_NORMAL or ln < 23 or off < 24 or off + ln > page_sz or off & 7:
+        return None
+    return off, ln
+
+
 def host_scan(data: bytes, page_sz: int = 8192, skip_invisible: bool = False,
               attr_off: int = -1, attr_width: int = 8, lo: int = -(1 << 63),
               hi: int = (1 << 63) - 1, verify_checksum: bool = False,
-              blkno_base: int = 0) -> Tuple[List[int], List[int]]:
-    """Reference scan: (sorted item ids page<<16|lineno, per-page status)."""
+              blkno_base: int = 0, blknos: Optional[Sequence[int]] = None
+              ) -> Tuple[List[int], List[int]]:
+    """Reference scan: (sorted item ids page<<16|lineno, per-page status).
+    A line pointer is followed when it is LP_NORMAL, lp_len >= 23,
+    lp_off >= 24, lp_off + lp_len <= page_sz and lp_off is MAXALIGNed."""
     items, status = [], []
     for pg in range(len(data) // page_sz):
         page = data[pg * page_sz:(pg + 1) * page_sz]
@@ -152,7 +170,7 @@ def host_scan(data: bytes, page_sz: int = 8192, skip_invisible: bool = False,
               or flags & ~7 or (psv & 0xFF00) != (page_sz & 0xFF00)):
             st |= 1
         if verify_checksum and not st:
-            if checksum(page, blkno_base + pg) != ck:
+            if checksum(page, blknos[pg] if blknos is not None else blkno_base + pg) != ck:
                 st |= 2
         status.append(st)
         if st:
@@ -160,7 +178,7 @@ def host_scan(data: bytes, page_sz: int = 8192, skip_invisible: bool = False,
         for i in range((lower - 24) // 4):
             lp, = struct.unpack_from("<I", page, 24 + 4 * i)
             off, fl, ln = lp & 0x7FFF, (lp >> 15) & 3, lp >> 17
-            if fl != LP_NORMAL or ln < 23 or off < 24 or off + ln > page_sz:
+            if fl != LP_NORMAL or ln < 23 or off < 24 or off + ln > page_sz or off & 7:
                 continue
             infomask, = struct.unpack_from("<H", page, off + 20)
             hoff = page[off + 22]

@@ -262,54 +262,169 @@ def build_pages(rows: Sequence[Sequence[Any]], desc: TupleDesc, page_sz: int = 8
     return b"".join(pages)
 
 
-def deform(tup: bytes, desc: TupleDesc) -> List[Any]:
-    """Attribute values of a tuple (None for NULL / not stored, EXT for a
-    compressed or out-of-line varlena); raises ValueError when malformed."""
-    infomask2, infomask = struct.unpack_from("<HH", tup, 18)
-    hoff = tup[22]
-    natts = infomask2 & 0x7FF
-    hasnull = bool(infomask & HEAP_HASNULL)
-    out, off = [], hoff
-    for i in range(desc.natts):
-        if i >= natts or (hasnull and not (tup[23 + (i >> 3)] >> (i & 7)) & 1):
-            out.append(None)
-            continue
+class _Walk:
+    """One tuple's attribute walk, as far as it is well formed.
+
+    The rules for a malformed tuple, stated once (they are the kernels',
+    csrc/kernels/heapscan.hip deform_init / deform_to, which follow
+    PostgreSQL's slot_deform_heap_tuple):
+
+    * the header is bad — and every attribute of the tuple with it — when
+      t_hoff < 24 or is not MAXALIGNed (PostgreSQL places attributes relative
+      to a MAXALIGNed t_hoff), t_hoff > lp_len, or HEAP_HASNULL is set and the
+      null bitmap of the stored attribute count does not fit below t_hoff;
+    * an attribute beyond the stored count (t_infomask2) is NULL, whatever the
+      rest of the tuple looks like;
+    * the walk goes only as far as the highest attribute asked for: storage
+      behind it is never looked at, so a malformed later attribute does not
+      spoil an earlier one;
+    * the walk stops at the first attribute whose storage is malformed — a
+      fixed-length value, varlena or cstring running past lp_len, a 4-byte
+      varlena header whose length is below 4, a TOAST pointer with an unknown
+      tag or cut short — and that attribute and every later stored one is bad.
+    """
+
+    def __init__(self, tup: bytes, desc: TupleDesc):
+        self.tup, self.desc = tup, desc
+        infomask2, infomask = struct.unpack_from("<HH", tup, 18)
+        self.hoff = tup[22]
+        self.natts = infomask2 & 0x7FF
+        self.hasnull = bool(infomask & HEAP_HASNULL)
+        self.header_bad = (self.hoff < 24 or self.hoff & 7 or self.hoff > len(tup) or
+                           (self.hasnull and 23 + ((self.natts + 7) >> 3) > self.hoff))
+        self.vals: List[Any] = []       # attributes walked so far
+        self.spans: List[Any] = []      # (data offset, data length, ext) of varlenas / cstrings
+        self.off = self.hoff
+        self.bad_at: Optional[int] = 0 if self.header_bad else None
+
+    def _step(self) -> None:
+        """Walk one more attribute (index len(self.vals)); ValueError when malformed."""
+        tup, desc, i, off = self.tup, self.desc, len(self.vals), self.off
+        if self.hasnull and not (tup[23 + (i >> 3)] >> (i & 7)) & 1:
+            self.vals.append(None)
+            self.spans.append(None)
+            return
         L, al, kind = desc.attlen[i], desc.attalign[i], desc.kinds[i]
+        span = None
         if L > 0:
             off = _align(off, al)
-            raw = tup[off:off + L]
-            if len(raw) < L:
+            if off + L > len(tup):
                 raise ValueError("attribute past the tuple end")
+            raw = tup[off:off + L]
             if kind == "float":
-                out.append(struct.unpack("<f" if L == 4 else "<d", raw)[0])
+                v = struct.unpack("<f" if L == 4 else "<d", raw)[0]
             elif kind == "bytes":
-                out.append(bytes(raw))
+                v = bytes(raw)
             else:
-                out.append(int.from_bytes(raw, "little", signed=True))
+                v = int.from_bytes(raw, "little", signed=True)
             off += L
         elif L == -1:
+            if off >= len(tup):
+                raise ValueError("varlena past the tuple end")
             if tup[off] == 0:                       # pad byte: aligned 4-byte header
                 off = _align(off, al)
+                if off >= len(tup):
+                    raise ValueError("varlena past the tuple end")
             b = tup[off]
             if b & 1 == 0:
+                if off + 4 > len(tup):
+                    raise ValueError("varlena header past the tuple end")
                 n = (struct.unpack_from("<I", tup, off)[0] >> 2) & 0x3FFFFFFF
-                out.append(EXT if b & 3 == 2 else bytes(tup[off + 4:off + n]))
+                if n < 4:
+                    raise ValueError("4-byte varlena header shorter than itself")
+                h, ext = 4, b & 3 == 2
             elif b == 1:
-                n = 2 + {18: 16, 1: 8, 2: 8, 3: 8}[tup[off + 1]]
-                out.append(EXT)
+                if off + 2 > len(tup):
+                    raise ValueError("TOAST pointer cut after its header")
+                size = {18: 16, 1: 8, 2: 8, 3: 8}.get(tup[off + 1])
+                if size is None:
+                    raise ValueError("unknown TOAST pointer tag")
+                n, h, ext = 2 + size, 2, True
             else:
-                n = b >> 1
-                out.append(bytes(tup[off + 1:off + n]))
-            if kind == "numeric" and out[-1] is not EXT:
-                out[-1] = numeric_value(out[-1])
+                n, h, ext = b >> 1, 1, False
             if off + n > len(tup):
                 raise ValueError("varlena past the tuple end")
+            v = EXT if ext else bytes(tup[off + h:off + n])
+            span = (off + h, n - h, ext)
+            if kind == "numeric" and v is not EXT:
+                v = numeric_value(v) if _numeric_ok(v) else BADNUM
             off += n
         else:
-            e = tup.index(b"\0", off)
-            out.append(bytes(tup[off:e]))
+            e = tup.find(b"\0", off)
+            if e < 0:
+                raise ValueError("cstring without a terminator")
+            v = bytes(tup[off:e])
+            span = (off, e + 1 - off, False)
             off = e + 1
-    return out
+        self.vals.append(v)
+        self.spans.append(span)
+        self.off = off
+
+    def get(self, k: int):
+        """The value of attribute ``k`` (None: NULL or not stored); ValueError
+        when the header, or an attribute up to ``k``, is malformed."""
+        if self.header_bad:
+            raise ValueError("bad tuple header")
+        if k >= self.natts:
+            return None
+        while self.bad_at is None and len(self.vals) <= k:
+            try:
+                self._step()
+            except ValueError:
+                self.bad_at = len(self.vals)
+        if self.bad_at is not None and k >= self.bad_at:
+            raise ValueError(f"attribute {self.bad_at} is malformed")
+        return self.vals[k]
+
+
+BADNUM = object()   # a numeric whose payload is no numeric: every comparison with it is false
+
+
+def _numeric_ok(raw: bytes) -> bool:
+    """Whether a varlena payload is an on-disk numeric: a 2-byte header (4 for
+    NumericLong), whole 2-byte digits, and of the special headers only NaN
+    (0xC000), +Infinity (0xD000) and -Infinity (0xF000)."""
+    if len(raw) < 2:
+        return False
+    h, = struct.unpack_from("<H", raw, 0)
+    if h & 0xC000 == 0xC000:
+        return h & 0xF000 != 0xE000
+    hdr = 2 if h & 0xC000 == 0x8000 else 4
+    return len(raw) >= hdr and (len(raw) - hdr) % 2 == 0
+
+
+def deform(tup: bytes, desc: TupleDesc) -> List[Any]:
+    """Attribute values of a tuple (None for NULL / not stored, EXT for a
+    compressed or out-of-line varlena); raises ValueError when the tuple is
+    malformed (see :class:`_Walk`, which walks only as far as it is asked)."""
+    w = _Walk(tup, desc)
+    return [w.get(k) for k in range(desc.natts)]
+
+
+def project_tuple(tup: bytes, desc: TupleDesc, attnos: Sequence[int], tuple_off: int = 0) -> list:
+    """What the projection gives for the attributes ``attnos`` of one tuple:
+    (value, valid) each — valid 0 NULL / not stored / malformed (value 0), 1 a
+    value (ints and floats as they are; varlenas and cstrings as (offset of
+    the data from ``tuple_off``, data length)), 2 a compressed or out-of-line
+    varlena (offset and length of what is stored)."""
+    w = _Walk(tup, desc)
+    out = {}
+    for k in sorted(attnos):
+        try:
+            v = w.get(k)
+        except ValueError:
+            out[k] = (0, 0)
+            continue
+        if v is None:
+            out[k] = (0, 0)
+        elif desc.attlen[k] < 0:
+            o, n, ext = w.spans[k]
+            out[k] = ((tuple_off + o, n), 2 if ext else 1)
+        elif desc.kinds[k] == "bytes":
+            out[k] = (int.from_bytes(v[:8], "little", signed=True), 1)
+        else:
+            out[k] = (v, 1)
+    return [out[k] for k in attnos]
 
 
 def _b(x) -> bytes:
@@ -348,6 +463,8 @@ class Qual:
                 return False                     # constant false, whatever v is
             if v is EXT:
                 return None
+            if v is BADNUM:
+                return False                     # no numeric: compares to nothing
             k = numeric_key(v)
             if self.op == "in":
                 return any(k == numeric_key(c) for c in self.args[0])
@@ -402,7 +519,7 @@ def _pg_le(x: float, y: float) -> bool:
 
 def host_scan2(data: bytes, desc: TupleDesc, quals: Sequence[Qual], page_sz: int = 8192,
                skip_invisible: bool = False, verify_checksum: bool = False,
-               blkno_base: int = 0, project=None) -> Tuple[List[int], List[int], list]:
+               blkno_base: int = 0, project=None, blknos=None) -> Tuple[List[int], List[int], list]:
     """Reference scan with a qualifier list: (sorted item ids page<<16|lineno,
     per-page status incl. PAGE_RECHECK, projected values of the items: one
     value per item, a tuple of values when ``project`` lists columns)."""
@@ -413,7 +530,7 @@ def host_scan2(data: bytes, desc: TupleDesc, quals: Sequence[Qual], page_sz: int
     for pg in range(len(data) // page_sz):
         page = data[pg * page_sz:(pg + 1) * page_sz]
         _, st = pgpage.host_scan(page, page_sz, False, verify_checksum=verify_checksum,
-                                 blkno_base=blkno_base + pg)
+                                 blkno_base=blknos[pg] if blknos is not None else blkno_base + pg)
         st = st[0]
         if st:
             status.append(st)
@@ -423,39 +540,47 @@ def host_scan2(data: bytes, desc: TupleDesc, quals: Sequence[Qual], page_sz: int
         for i in range((lower - 24) // 4):
             lp, = struct.unpack_from("<I", page, 24 + 4 * i)
             off, fl, ln = lp & 0x7FFF, (lp >> 15) & 3, lp >> 17
-            if fl != pgpage.LP_NORMAL or ln < 23 or off < 24 or off + ln > page_sz or off & 1:
+            if fl != pgpage.LP_NORMAL or ln < 23 or off < 24 or off + ln > page_sz or off & 7:
                 continue
             tup = page[off:off + ln]
             infomask, = struct.unpack_from("<H", tup, 20)
             if skip_invisible and not pgpage.tuple_visible(infomask, flags):
                 continue
-            try:
-                vals = deform(tup, desc)
-            except (ValueError, KeyError, IndexError):
-                continue
             # CNF, three-valued: a clause is true if any of its quals is,
-            # unknown if none is but one is undecidable (EXT), else false
+            # unknown if none is but one is undecidable (EXT), else false.
+            # The tuple is deformed as the quals ask for attributes — a
+            # clause's quals by attribute, up to its first true one — and a
+            # malformed attribute met on the way drops the tuple.
+            walk = _Walk(tup, desc)
             verdict = True
-            for cl in clauses(quals):
-                cv = False
-                for q in cl:
-                    k = desc.attno(q.col)
-                    r = q.test(vals[k], desc.kinds[k])
-                    if r is True:
-                        cv = True
+            try:
+                for cl in clauses(quals):
+                    cv = False
+                    for q in sorted(cl, key=lambda q: desc.attno(q.col)):
+                        k = desc.attno(q.col)
+                        r = q.test(walk.get(k), desc.kinds[k])
+                        if r is True:
+                            cv = True
+                            break
+                        if r is None:
+                            cv = None
+                    if cv is False:
+                        verdict = False
                         break
-                    if r is None:
-                        cv = None
-                if cv is False:
-                    verdict = False
-                    break
-                if cv is None:
-                    verdict = None
+                    if cv is None:
+                        verdict = None
+            except ValueError:
+                continue
             if verdict is None:
                 st |= PAGE_RECHECK
             elif verdict:
-                found.append((i + 1, tuple(vals[k] for k in pj) if many else
-                              vals[pj] if pj is not None else None))
+                def val(k):
+                    try:
+                        return walk.get(k)
+                    except ValueError:
+                        return None
+                found.append((i + 1, tuple(val(k) for k in pj) if many else
+                              val(pj) if pj is not None else None))
         status.append(st)
         for lineno, v in found:
             items.append((pg << 16) | lineno)

@@ -167,6 +167,15 @@ build/heapscan_fuzz: csrc/tests/heapscan_fuzz.cc csrc/kernels/heapscan.hip csrc/
 	  -Xarch_host -fno-sanitize-recover=all -fno-omit-frame-pointer \
 	  -o $@ csrc/tests/heapscan_fuzz.cc csrc/kernels/heapscan.hip
 
+# the computed-column kernel's host copy (program check, loads, ops, validity
+# words), host-only with ASan + UBSan
+build/colexpr_fuzz: csrc/tests/colexpr_fuzz.cc csrc/kernels/colexpr.hip csrc/include/strom/strom.h
+	@mkdir -p build
+	$(HIPCC) -std=c++17 -O1 -g -Icsrc/include --offload-arch=$(ARCH) \
+	  -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
+	  -Xarch_host -fno-sanitize-recover=all -fno-omit-frame-pointer \
+	  -o $@ csrc/tests/colexpr_fuzz.cc csrc/kernels/colexpr.hip
+
 selftest: build/selftest build/selftest-asan build/selftest-tsan
 	STROM_STAT_SHM=0 ./build/selftest && STROM_STAT_SHM=0 ./build/selftest-asan && STROM_STAT_SHM=0 TSAN_OPTIONS=report_signal_unsafe=0 ./build/selftest-tsan
 

@@ -967,6 +967,81 @@ int strom_topk_host_select(int type, uint32_t flags, uint32_t k, const uint64_t 
                            uint32_t nbatches, const uint64_t *state, uint64_t *slabs);
 int strom_topk_host_merge(uint32_t k, const uint64_t *slabs, uint32_t nslabs, uint64_t *state);
 
+/* Computed columns (csrc/kernels/colexpr.hip; Arrow scans: an E expression
+ * where a column name is accepted; nvme_strom_amd/ops/colexpr.py compiles
+ * them): one arithmetic expression over up to STROM_EXPR_MAX_COLS source
+ * columns, evaluated for every row of a group's batches in one launch into an
+ * 8-byte column that the qualifier, aggregate, group, top-k and emit kernels
+ * read like a stored one (STROM_COL_I64 or STROM_COL_F64).
+ *
+ * The program is a postfix list of at most STROM_EXPR_MAX_OPS ops over a
+ * stack of at most STROM_EXPR_MAX_DEPTH values, all of one domain:
+ *   STROM_EXPR_INT  sources I8 .. I64, U8 .. U32 sign-/zero-extended to int64;
+ *                   ADD SUB MUL NEG ABS wrap in 64 bits (NEG and ABS of
+ *                   INT64_MIN are INT64_MIN); FDIV and MOD by the immediate
+ *                   (> 0) round toward minus infinity, MOD within [0, imm).
+ *   STROM_EXPR_FLT  integer sources converted with (double), F32 widened; ADD
+ *                   SUB MUL DIV are IEEE double operations, each rounded on
+ *                   its own (never fused); NEG and ABS act on the sign bit.  A
+ *                   NaN result is stored as 0x7ff8000000000000.
+ * COL pushes source column arg, CONST the immediate (an int64, or the bits
+ * of a double).  F32 / F64 sources and DIV need the FLT domain, FDIV and MOD
+ * the INT domain.
+ *
+ * d_src holds ncols tables of nbatches entries (column c's at d_src + c *
+ * nbatches), all of the same batches; d_out is one more table of them whose
+ * values receive row i's result at ((uint64_t *)values)[i] and whose valid
+ * (never 0) receives whole validity words, word k of the batch at
+ * ((uint64_t *)valid)[k]: the AND of the sources' validity words (valid = 0:
+ * all ones), the batch's last word cut to nrows.  Only rows whose validity
+ * bit is set are loaded and stored.  d_sel (may be NULL) is a selection
+ * bitmap of nwords words: a word whose d_sel word is 0 is not evaluated, its
+ * validity word is stored as 0 and no value of it is stored.
+ *
+ * strom_expr_check: 0, or -22 for an unknown opcode or domain, no op or more
+ * than STROM_EXPR_MAX_OPS, more than STROM_EXPR_MAX_COLS columns, a column
+ * index >= ncols, a source type the domain does not take, an op of the other
+ * domain, an immediate divisor <= 0, a stack underflow, a depth above
+ * STROM_EXPR_MAX_DEPTH or a final depth other than 1.  strom_column_expr
+ * runs it first and launches nothing unless it passes.
+ * strom_column_expr_host is the same walk on the CPU over host pointers
+ * (csrc/tests/colexpr_fuzz.cc runs it under ASan + UBSan). */
+#define STROM_EXPR_MAX_OPS 16
+#define STROM_EXPR_MAX_COLS 4
+#define STROM_EXPR_MAX_DEPTH 8
+#define STROM_EXPR_INT 0
+#define STROM_EXPR_FLT 1
+#define STROM_XOP_COL 1
+#define STROM_XOP_CONST 2
+#define STROM_XOP_ADD 3
+#define STROM_XOP_SUB 4
+#define STROM_XOP_MUL 5
+#define STROM_XOP_NEG 6
+#define STROM_XOP_ABS 7
+#define STROM_XOP_DIV 8
+#define STROM_XOP_FDIV 9
+#define STROM_XOP_MOD 10
+struct strom_expr_op {
+	uint32_t op;
+	uint32_t arg;          /* COL: the source column */
+	uint64_t imm;          /* CONST, FDIV, MOD */
+};
+struct strom_expr {
+	uint32_t domain;
+	uint32_t nops;
+	uint32_t ncols;
+	uint32_t reserved;
+	uint32_t col_type[STROM_EXPR_MAX_COLS];
+	struct strom_expr_op ops[STROM_EXPR_MAX_OPS];
+};
+int strom_expr_check(const struct strom_expr *e);
+int strom_column_expr(const struct strom_expr *e, const struct strom_filter_batch *d_src,
+                      uint32_t nbatches, uint64_t nwords, const uint64_t *d_sel,
+                      const struct strom_filter_batch *d_out, void *stream);
+int strom_column_expr_host(const struct strom_expr *e, const struct strom_filter_batch *src,
+                           uint32_t nbatches, uint64_t nwords, const uint64_t *sel,
+                           const struct strom_filter_batch *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,13 +45,14 @@ from ..ops import colgroup as G
 from ..ops import coljoin as J
 from ..ops import coltopk as T
 from ..ops import decompress as D
+from ..ops.colexpr import E, ExprName, Program, compile_expr, expr_batched, host_expr, name_of
 from ..ops.colfilter import BATCH_FIELDS, bitmap_to_rows, bitmap_to_rows_str
 from ..ops.colpred import (COL_CODE, QUAL_BATCH_FIELDS, Compiled, Pred, clauses, compile_pred,
                            evaluate, qual_batched)
 from ..ops.reorder import chunk_scatter, landing_positions
 from ..tensor import FileReader, HbmBuffer, host_buffer
-from ..utils.arrow_ipc import (ArrowFile, Column, _Src, decode_values, dictionary_values,
-                               read_buffer, read_metadata, validity_bits)
+from ..utils.arrow_ipc import (ArrowFile, Column, ColumnArrays, _Src, decode_values,
+                               dictionary_values, read_buffer, read_metadata, validity_bits)
 
 # projection output dtypes by storage (date/time/timestamp/duration: their
 # integer ticks; dictionary-encoded: the indices)
@@ -187,13 +188,17 @@ class JoinTable:
 class Join:
     """``join=Join("fk", dim, how="semi")``: keep the rows whose ``fk`` is a
     key of ``dim`` (``how="anti"``: the rows whose ``fk`` is not; a null fk
-    matches nothing, so the anti-join keeps it, as pyarrow's "left anti")."""
+    matches nothing, so the anti-join keeps it, as pyarrow's "left anti").
+    ``fk`` is a stored column: an expression (ops/colexpr.E) is refused."""
 
     def __init__(self, col: str, table: JoinTable, how: str = "semi"):
         if how not in J.HOW:
             raise ValueError(f"join how={how!r}: one of {sorted(J.HOW)}")
         if not isinstance(table, JoinTable):
             raise TypeError("Join: the build side is a JoinTable")
+        if isinstance(col, E):
+            raise NotImplementedError(f"join on {col!r}: a computed column is not a join key "
+                                      "(stored integer columns are)")
         self.col, self.table, self.how = str(col), table, how
 
 
@@ -257,7 +262,12 @@ class HashBy:
     ``col``'s values lie in [-2^(n-1), 2^(n-1)) (signed) or [0, 2^n); a
     selected row outside that range raises RuntimeError at the sync.
     ``groups`` counts distinct tuples.  Rows come back in lexicographic
-    order, each column ascending, nulls last (an attribute by its code)."""
+    order, each column ascending, nulls last (an attribute by its code).
+
+    A key or a component may be an int64 expression (ops/colexpr.E:
+    ``HashBy(E("ts_ms") // 86_400_000, groups)``), computed on the device per
+    group before the table is probed; as a component it takes 64 bits (65 when
+    a source column has nulls) unless ``bits={expr: n}`` declares fewer."""
 
     def __init__(self, col, groups: int = 1 << 16, bits: Optional[dict] = None):
         self.groups = G.check_groups(groups)
@@ -270,7 +280,8 @@ class HashBy:
             if len(comps) > G.MAX_KEYS:
                 raise NotImplementedError(f"HashBy of {len(comps)} components: at most "
                                           f"{G.MAX_KEYS} are packed into the 64-bit key")
-            comps = [c if isinstance(c, JoinAttr) else str(c) for c in comps]
+            comps = [c if isinstance(c, (JoinAttr, ExprName)) else
+                     (name_of(c) if isinstance(c, E) else str(c)) for c in comps]
             names = [("attr", id(c.table), c.name) if isinstance(c, JoinAttr) else ("col", c)
                      for c in comps]
             for n in names:
@@ -282,6 +293,7 @@ class HashBy:
                                           "probe writes one attribute's codes per leg)")
             cols = [c for c in comps if not isinstance(c, JoinAttr)]
             for n, b in (bits or {}).items():
+                n = name_of(n)
                 if n not in cols:
                     raise ValueError(f"bits= names {n!r}, which is not a column of the key")
                 if isinstance(b, bool) or int(b) != b or not 1 <= int(b) <= 64:
@@ -296,7 +308,7 @@ class HashBy:
         else:
             if bits:
                 raise ValueError("bits= belongs to a list of key columns")
-            self.col = str(col)
+            self.col = name_of(col) if isinstance(col, (E, ExprName)) else str(col)
 
     @property
     def attrs(self) -> List[JoinAttr]:
@@ -345,6 +357,74 @@ def _check_join(meta: ArrowFile, join, attrs):
     return join
 
 
+MAX_EXPRS = 4          # computed columns per scan: 8 B of slot memory per row each
+
+
+class _ExprMeta:
+    """A file's metadata with a scan's computed columns appended: their
+    synthetic Columns behind the schema's, and per expression a ColumnArrays
+    whose null counts are its source columns' added up (nulls somewhere in the
+    file, batch by batch).  Everything else is the file's.  The validators
+    (_agg_spec, _top_spec, _key_spec, compile_pred) then see a computed column
+    as they see a stored int64 / float64 one."""
+
+    def __init__(self, meta: ArrowFile, progs: Dict[str, Program]):
+        self._meta, self.progs = meta, progs
+        self.schema = list(meta.schema) + [p.column for p in progs.values()]
+        self.columns = list(meta.columns)
+        for p in progs.values():
+            src = [meta.columns[meta.column_index(n)] for n in p.columns]
+            self.columns.append(ColumnArrays(
+                src[0].length, sum(np.asarray(a.null_count, np.int64) for a in src),
+                src[0].v_off, src[0].v_len, src[0].d_off, src[0].d_len))
+
+    def __getattr__(self, name):
+        return getattr(self._meta, name)
+
+    def column_index(self, name: str) -> int:
+        for i, c in enumerate(self.schema):
+            if c.name == name:
+                return i
+        raise KeyError(name)
+
+
+def _named_clauses(quals) -> List[List[Pred]]:
+    """clauses(quals) with every expression a predicate is on by its name."""
+    return [[replace(p, col=name_of(p.col)) if isinstance(p.col, E) else p for p in c]
+            for c in clauses(quals)]
+
+
+def _with_exprs(meta: ArrowFile, names) -> ArrowFile:
+    """``meta``, or an _ExprMeta over it when ``names`` (the column names of a
+    query, expressions as ExprName) hold computed columns: each distinct
+    expression compiled once."""
+    progs: Dict[str, Program] = {}
+    schema = {c.name: c for c in meta.schema}
+    for n in names:
+        if not isinstance(n, ExprName) or n in progs:
+            continue
+        if n in schema:
+            raise ValueError(f"the file has a column named {str(n)!r}: the expression cannot go "
+                             "by that name")
+        if len(progs) == MAX_EXPRS:
+            raise ValueError(f"more than {MAX_EXPRS} computed columns in one scan")
+        progs[n] = compile_expr(n.expr, schema, nulls=lambda c: _file_nulls(meta, c))
+    return _ExprMeta(meta, progs) if progs else meta
+
+
+def _split_names(meta, names: List[str]) -> Tuple[List[str], List[str]]:
+    """(the stored columns a scan reads — ``names`` without the computed
+    columns, then their source columns —, those followed by the computed
+    columns: the index of a name there is its column number in the scan)."""
+    progs = getattr(meta, "progs", None)
+    if not progs:
+        return names, names
+    stored = [n for n in names if n not in progs]
+    for p in progs.values():
+        stored += [c for c in p.columns if c not in stored]
+    return stored, stored + list(progs)
+
+
 @dataclass
 class ScanOut:
     rows: int
@@ -360,6 +440,7 @@ class ScanOut:
     dictionary: object = None               # its decoded dictionary when dictionary-encoded
     offsets: Optional[torch.Tensor] = None  # utf8/binary projection: int64[selected + 1]
                                             # into ``values`` (the characters, uint8)
+    exprs: list = field(default_factory=list)   # the computed columns' Programs
 
 
 @dataclass
@@ -407,6 +488,14 @@ class _TopRun:
 
 
 @dataclass
+class _ExprRun:
+    """One computed column of a scan as _compute sees it."""
+    prog: Program
+    cols: List[int]               # plan columns of its sources
+    early: bool                   # a qualifier reads it: evaluated before the filter
+
+
+@dataclass
 class _Run:
     """One scan as _compute's stages see it: its totals over the groups and
     where its results go.  A stage whose field is None is not called."""
@@ -419,6 +508,7 @@ class _Run:
     join: Optional[_JoinRun] = None
     hash: Optional[_HashRun] = None
     top: Optional[_TopRun] = None
+    exprs: List[_ExprRun] = field(default_factory=list)   # column len(names) + j each
     # rows (scan_where): the row ids and the projection behind their cursors
     out: Optional[torch.Tensor] = None
     cursor: Optional[torch.Tensor] = None
@@ -535,6 +625,10 @@ class _Slot:
     keybuf: Optional[torch.Tensor] = None  # int32 per row: the joined attribute's code
     # a StarJoin's attribute legs: one more such buffer each, reused like keybuf
     legbuf: List[torch.Tensor] = field(default_factory=list)
+    # computed columns: per expression 8 bytes per row of the bitmap and its
+    # validity words, allocated on first use and kept for the slot's later groups
+    exprbuf: List[torch.Tensor] = field(default_factory=list)
+    exprvalid: List[torch.Tensor] = field(default_factory=list)
     pin_off: int = 0
 
 
@@ -546,10 +640,19 @@ class _Tables:
         self.upload, self.s, self.g, self.base, self.dec_base = upload, s, g, base, dec_base
         self.tabs: Dict[int, torch.Tensor] = {}
         self.tabs_np: Dict[int, np.ndarray] = {}
+        self.xtabs: Optional[torch.Tensor] = None    # the expression stage's tables
 
     def _host(self, col: int) -> np.ndarray:
         """The group's strom_qual_batch table for one column: values,
-        validity and character pointers resolved against this slot."""
+        validity and character pointers resolved against this slot.  A
+        column number past the plan's is a computed column: batch b's results
+        at row word_base * 64 of the slot's buffer for it, their validity
+        words at word word_base."""
+        if col not in self.tabs_np and col >= self.g.ptr_kind.shape[1]:
+            g, j = self.g, col - self.g.ptr_kind.shape[1]
+            t = self.tabs_np[col] = g.table.copy()
+            t[:, 0] = self.s.exprbuf[j].data_ptr() + g.table[:, 3] * 512
+            t[:, 1] = self.s.exprvalid[j].data_ptr() + g.table[:, 3] * 8
         if col not in self.tabs_np:
             g = self.g
             t = self.tabs_np[col] = g.table.copy()
@@ -1061,6 +1164,9 @@ class ArrowScan:
         with torch.cuda.stream(s.stream):
             self._decode(k, s, g, region, run)
             t = _Tables(self._upload, s, g, region.data_ptr(), s.dec.data_ptr())
+            if run.exprs:
+                # the computed columns a qualifier reads, over every row
+                self._evaluate(s, g, t, run, True, None)
             bitmap = self._filter(s, g, t, spec, counts=run.join is None)
             # the table of the slot's key buffer once a stage writes codes there
             d_codes = None
@@ -1070,6 +1176,9 @@ class ArrowScan:
                     # project= / by=dim[attr] / top carry one attribute: leg
                     # buffer 0 (a HashBy of several reads them by its own tables)
                     d_codes = d_codes[0]
+            if run.exprs:
+                # the others, over the words that still select something
+                self._evaluate(s, g, t, run, False, bitmap)
             if run.hash is not None:
                 bitmap, d_codes = self._group_codes(s, g, t, run.hash, bitmap)
             run.marks.append((k, "quals_queued", time.perf_counter()))
@@ -1167,6 +1276,46 @@ class ArrowScan:
         bitmap = self._upload(s, g.ones)
         s.keep.append(bitmap)
         return bitmap
+
+    def _evaluate(self, s: _Slot, g: _Group, t: _Tables, run: _Run, early: bool,
+                  sel: Optional[torch.Tensor]) -> None:
+        """The computed columns of one stage (csrc/kernels/colexpr.hip), one
+        launch each: ``early`` those a qualifier reads, before the filter and
+        over every row; the others after the probe with the selection ``sel``,
+        so that a word no row of which is selected costs nothing.  The source
+        tables of all of the group's expressions and the tables of their
+        buffers go up in one copy, at the first stage that runs."""
+        todo = [x for x in run.exprs if x.early == early]
+        if not todo:
+            return
+        nst = g.ptr_kind.shape[1]
+        if t.xtabs is None:
+            rows = s.bitmap.numel() * 64
+            while len(s.exprbuf) < len(run.exprs):
+                s.exprbuf.append(torch.empty(rows, dtype=torch.int64, device=self.device))
+                s.exprvalid.append(torch.empty(rows // 64, dtype=torch.int64, device=self.device))
+            for j in range(len(run.exprs)):
+                if s.exprbuf[j].numel() < rows:
+                    s.exprbuf[j] = torch.empty(rows, dtype=torch.int64, device=self.device)
+                    s.exprvalid[j] = torch.empty(rows // 64, dtype=torch.int64,
+                                                 device=self.device)
+            t.xtabs = self._upload(s, np.stack(
+                [t.host5(c) for x in run.exprs for c in x.cols] +
+                [t.host5(nst + j) for j in range(len(run.exprs))]))
+            s.keep.append(t.xtabs)
+        nsrc = sum(len(x.cols) for x in run.exprs)
+        o = 0
+        for j, x in enumerate(run.exprs):
+            if x.early == early:
+                expr_batched(x.prog, t.xtabs[o:o + len(x.cols)], g.words, t.xtabs[nsrc + j], sel,
+                             stream=s.stream)
+            o += len(x.cols)
+
+    def _expr_runs(self, meta, full: List[str], cl) -> List[_ExprRun]:
+        """The scan's computed columns (``meta``: _with_exprs) for _compute."""
+        qual = {p.col for c in cl for p in c}
+        return [_ExprRun(p, [full.index(c) for c in p.columns], n in qual)
+                for n, p in getattr(meta, "progs", {}).items()]
 
     def _code_table(self, s: _Slot, g: _Group, leg: int = -1) -> np.ndarray:
         """The batch table of the slot's key buffer, or of its buffer for the
@@ -1344,10 +1493,11 @@ class ArrowScan:
         (values, valid) as utils.arrow_ipc.dictionary_values returns them."""
         return _dictionary(self.meta, self.path, self._dicts, name)
 
-    def _compile(self, p: Pred) -> Compiled:
+    def _compile(self, p: Pred, meta=None) -> Compiled:
         key = (p.col, p.op, repr(p.value))
         if key not in self._compiled:
-            col = self.meta.schema[self.meta.column_index(p.col)]
+            meta = meta if meta is not None else self.meta
+            col = meta.schema[meta.column_index(p.col)]
             self._compiled[key] = _compile_pred(p, col, self.dictionary)
         return self._compiled[key]
 
@@ -1461,21 +1611,28 @@ class ArrowScan:
         joined attribute's code per selected row (``ScanOut.dictionary``
         holds the codes' values).  ``join=StarJoin(Join(...), Join(...), ...)``
         applies up to four such legs in that one launch (a row is kept if every
-        leg keeps it); ``dim[attr]`` then names the leg whose table is ``dim``."""
+        leg keeps it); ``dim[attr]`` then names the leg whose table is ``dim``.
+        A predicate may be on an expression (ops/colexpr.E: ``E("a") + E("b") <
+        5``, every numeric operator) and ``project`` may be one (its int64 or
+        float64 values): computed on the device per group (colexpr.hip), at
+        most four distinct expressions per scan."""
         pattr = project if isinstance(project, JoinAttr) else None
         join = _check_join(self.meta, join, pattr)
         if pattr is not None:
             project = None
-        cl = clauses(quals) if (quals or join is None) else []
+        project = name_of(project)
+        cl = _named_clauses(quals) if (quals or join is None) else []
         t0 = time.perf_counter()
         names = _scanned(cl, join, [project] if project else [])
+        xm = _with_exprs(self.meta, names)
+        names, full = _split_names(xm, names)
         cols, nrows, groups = self._resolve(names, batches)
-        spec = [[(names.index(p.col), self._compile(p)) for p in c] for c in cl]
+        spec = [[(full.index(p.col), self._compile(p, xm)) for p in c] for c in cl]
         t_plan = time.perf_counter()
         out = torch.empty(max(nrows, 1), dtype=torch.int64, device=self.device)
-        pcol = names.index(project) if project else None
+        pcol = full.index(project) if project else None
         pout = pvalid = pchars = poff = None
-        pmeta = cols[pcol] if project else None
+        pmeta = xm.schema[xm.column_index(project)] if project else None
         pstrings = bool(project) and pmeta.kind in ("utf8", "binary") and pmeta.dictionary is None
         if project:
             st = pmeta.storage
@@ -1492,7 +1649,8 @@ class ArrowScan:
                                           "utf8/binary or dictionary-encoded columns")
             else:
                 pout = torch.empty(max(nrows, 1), dtype=_TORCH[st], device=self.device)
-            if any(bool(g.has_valid[pcol]) for g in groups):
+            if pmeta.nullable if pcol >= len(names) else \
+                    any(bool(g.has_valid[pcol]) for g in groups):
                 pvalid = torch.empty(max(nrows, 1), dtype=torch.uint8, device=self.device)
         pdict = self.dictionary(project) if project and pmeta.dictionary is not None else None
         if pattr is not None:
@@ -1507,7 +1665,7 @@ class ArrowScan:
         run = _Run(self._zero(), self._zero(), out=out, cursor=self._zero(),
                    ccursor=self._zero(), pout=pout, pvalid=pvalid, pchars=pchars, poff=poff,
                    owidth=8 if pstrings and pmeta.large else 4, pattr=pattr is not None,
-                   pcol=pcol)
+                   pcol=pcol, exprs=self._expr_runs(xm, full, cl))
         if join is not None:
             run.join = self._join_run(join, names, pattr)
         t_alloc = self._drive(groups, spec, run)
@@ -1529,7 +1687,8 @@ class ArrowScan:
                        values=pout[:count] if pout is not None else
                        (pchars[:nchars] if pchars is not None else None),
                        valid=pvalid[:count] if pvalid is not None else None,
-                       column=pmeta, dictionary=pdict, offsets=offsets)
+                       column=pmeta, dictionary=pdict, offsets=offsets,
+                       exprs=[x.prog for x in run.exprs])
 
     def aggregate(self, quals, aggs, by=None, batches: Optional[Tuple[int, int]] = None,
                   join: Union[Join, StarJoin, None] = None) -> "AggOut":
@@ -1566,7 +1725,15 @@ class ArrowScan:
         code into the slot's key buffer and the aggregate kernels take it as
         their key column.  With ``join=StarJoin(...)`` each attribute leg
         writes a code buffer of its own, and ``HashBy([dimA[x], dimB[y], ...])``
-        groups by attributes of different JoinTables.  See AggOut."""
+        groups by attributes of different JoinTables.
+
+        Where a column is named, an expression (ops/colexpr.E) may stand: as
+        the column of an aggregate (``("sum", E("price") * E("qty"))``), in a
+        qualifier, as the key of ``HashBy`` (int64 expressions) or one of its
+        components (``bits={expr: n}``).  ``by=`` itself takes no expression:
+        the LDS-slot GROUP BY needs a stored key column.  At most four
+        distinct expressions per scan; one that a qualifier and an aggregate
+        share is computed once.  See AggOut."""
         t0 = time.perf_counter()
         battr = by if isinstance(by, JoinAttr) else None
         hb = by if isinstance(by, HashBy) else None
@@ -1574,16 +1741,18 @@ class ArrowScan:
         join = _check_join(self.meta, join, jattrs)
         if battr is not None or hb is not None:
             by = None
-        cl = clauses(quals) if quals else []
-        agg = _agg_spec(self.meta, aggs, by, self.dictionary, battr, hb)
+        cl = _named_clauses(quals) if quals else []
+        aggs, xm = _agg_exprs(self.meta, cl, aggs, by, hb)
+        agg = _agg_spec(xm, aggs, by, self.dictionary, battr, hb)
         names = _scanned(cl, join, agg.names)
+        names, full = _split_names(xm, names)
         cols, nrows, groups = self._resolve(names, batches)
         if not names:
             # count(*) of everything: the footer answers
             block = A.new_block(agg.layout)
             block[agg.layout.pos(0, A.COUNT)] = np.uint64(nrows)
             return _agg_out(agg, block, nrows, {"total_s": time.perf_counter() - t0})
-        spec = [[(names.index(p.col), self._compile(p)) for p in c] for c in cl]
+        spec = [[(full.index(p.col), self._compile(p, xm)) for p in c] for c in cl]
         t_plan = time.perf_counter()
         if not groups or nrows == 0:
             secs = {"total_s": time.perf_counter() - t0}
@@ -1591,10 +1760,10 @@ class ArrowScan:
                 return _agg_out(agg, A.new_block(agg.layout), nrows, secs)
             return _hash_out(agg, G.empty_groups(agg.layout.entries, agg.hash_unsigned,
                                                  agg.keyspec), nrows, secs)
-        agg.entry_cols = [None if n is None else names.index(n) for n in agg.entry_names]
+        agg.entry_cols = [None if n is None else full.index(n) for n in agg.entry_names]
         # by=dim[attr]: no file column, the key is the probe's code buffer
-        agg.key_col = names.index(by) if by is not None else None
-        run = _Run(self._zero(), self._zero(), agg=agg)
+        agg.key_col = full.index(by) if by is not None else None
+        run = _Run(self._zero(), self._zero(), agg=agg, exprs=self._expr_runs(xm, full, cl))
         if join is not None:
             run.join = self._join_run(join, names, jattrs)
         # the block is initialised on the emit stream, where the reduces follow
@@ -1612,12 +1781,12 @@ class ArrowScan:
             # order of the components; a Join's one attribute the key buffer
             star = isinstance(join, StarJoin)
             run.hash = _HashRun(-1, 0, dev, [None if isinstance(c, JoinAttr) else
-                                             names.index(c) for c in hb.comps],
+                                             full.index(c) for c in hb.comps],
                                 [hb.attrs.index(c) if star and isinstance(c, JoinAttr) else -1
                                  for c in hb.comps])
         elif hb is not None:
-            kc = self.meta.schema[self.meta.column_index(hb.col)]
-            run.hash = _HashRun(names.index(hb.col), G.KEY_CODE[kc.storage], dev)
+            kc = xm.schema[xm.column_index(hb.col)]
+            run.hash = _HashRun(full.index(hb.col), G.KEY_CODE[kc.storage], dev)
         run.block_ready = torch.cuda.Event()
         run.block_ready.record(es)
         t_alloc = self._drive(groups, spec, run)
@@ -1670,18 +1839,24 @@ class ArrowScan:
         bytes, a dictionary-encoded column's indices (``TopOut.dictionary``
         holds the values) or ``dim[attr]`` of the semi-join.  ``quals`` (may
         be empty), ``batches`` and ``join`` as in scan_where.  One order
-        column, no OFFSET.  See TopOut."""
+        column, no OFFSET.  ``order_by`` (and ``project``, and a qualifier's
+        column) may be an expression (ops/colexpr.E), computed on the device
+        per group: a float64 one orders its NaNs and nulls as a stored column's.
+        See TopOut."""
         t0 = time.perf_counter()
         k = T.check_k(k)
         pattr = project if isinstance(project, JoinAttr) else None
         join = _check_join(self.meta, join, pattr)
         if pattr is not None:
             project = None
-        spec_out = _top_spec(self.meta, order_by, k, descending, project, pattr, self.dictionary)
-        cl = clauses(quals) if quals else []
+        order_by, project = _order_name(order_by), name_of(project)
+        cl = _named_clauses(quals) if quals else []
         names = _scanned(cl, join, [order_by] + ([project] if project else []))
+        xm = _with_exprs(self.meta, names)
+        spec_out = _top_spec(xm, order_by, k, descending, project, pattr, self.dictionary)
+        names, full = _split_names(xm, names)
         cols, nrows, groups = self._resolve(names, batches)
-        spec = [[(names.index(p.col), self._compile(p)) for p in c] for c in cl]
+        spec = [[(full.index(p.col), self._compile(p, xm)) for p in c] for c in cl]
         t_plan = time.perf_counter()
         none = np.zeros((0, T.ENTRY_WORDS), np.uint64)
         if not groups or nrows == 0:
@@ -1690,10 +1865,10 @@ class ArrowScan:
         es = self._emit_stream()
         with torch.cuda.stream(es):
             state = T.init(k, self.device, stream=es)
-        run = _Run(self._zero(), self._zero())
-        run.top = _TopRun(names.index(order_by), T.TYPE_CODE[spec_out.column.storage],
+        run = _Run(self._zero(), self._zero(), exprs=self._expr_runs(xm, full, cl))
+        run.top = _TopRun(full.index(order_by), T.TYPE_CODE[spec_out.column.storage],
                           bool(descending), state,
-                          names.index(project) if project else None,
+                          full.index(project) if project else None,
                           4 if pattr is not None else
                           (np.dtype(spec_out.pcolumn.storage).itemsize if project else 0),
                           pattr is not None)
@@ -1763,6 +1938,28 @@ class HostScanOut:
     values: object = None              # projected values (numpy; strings: list of bytes)
     valid: Optional[np.ndarray] = None
     dictionary: object = None          # project=dim[attr]: the value of each code
+    exprs: list = field(default_factory=list)   # the computed columns' Programs
+
+
+def _order_name(order_by):
+    """``order_by`` of top / host_top as a column name."""
+    if not isinstance(order_by, (str, E)):
+        raise NotImplementedError("ORDER BY one column (a list of order columns is not supported)")
+    return name_of(order_by)
+
+
+def _agg_exprs(meta: ArrowFile, cl, aggs, by, hb: Optional[HashBy]) -> tuple:
+    """(``aggs`` with expressions by their names, the metadata with the
+    computed columns of the qualifiers ``cl``, the aggregates and the HashBy
+    key) of aggregate / host_aggregate."""
+    if isinstance(by, (E, ExprName)):
+        raise NotImplementedError(f"GROUP BY {by!r}: by= names a stored key column (its values "
+                                  "index accumulators in LDS); by=HashBy(expression) groups by a "
+                                  "computed one")
+    aggs = [(fn, name_of(col)) for fn, col in aggs]
+    keys = [] if hb is None else ([hb.col] if hb.comps is None else
+                                  [c for c in hb.comps if not isinstance(c, JoinAttr)])
+    return aggs, _with_exprs(meta, [p.col for c in cl for p in c] + [c for _, c in aggs] + keys)
 
 
 def _host_join(join: Join, v, ok, m: np.ndarray):
@@ -1813,7 +2010,12 @@ def _host_batches(path: str, meta: ArrowFile, dicts: dict, cl, join,
             if p.col not in schema:
                 raise ValueError(f"no column {p.col!r}")
         comp.append([(p.col, _compile_pred(p, schema[p.col][1], dictionary)) for p in c])
-    must = set(_scanned(cl, join, []))
+    # computed columns (meta: _with_exprs): their sources are read whole,
+    # they themselves come from the kernel's numpy twin
+    progs = getattr(meta, "progs", {})
+    must = (set(_scanned(cl, join, [])) | {c for p in progs.values() for c in p.columns}) - \
+        set(progs)
+    more = [n for n in more if n not in progs]
     nb = meta.nbatches
     b0, b1 = (0, nb) if batches is None else (max(0, batches[0]), min(nb, batches[1]))
     src = _Src(path)
@@ -1835,6 +2037,9 @@ def _host_batches(path: str, meta: ArrowFile, dicts: dict, cl, join,
                 x = read_buffer(src, ch.extra, b.codec) if (ch.extra is not None and
                                                             col.dictionary is None) else b""
                 data[n] = (decode_values(vcol, ch.length, d, x), ok)
+            for n, p in progs.items():
+                data[n] = host_expr(p, [data[c][0] for c in p.columns],
+                                    [data[c][1] for c in p.columns], b.length)
             m = np.ones(b.length, bool)
             for c in comp:
                 cm = np.zeros(b.length, bool)
@@ -1866,7 +2071,9 @@ def host_scan_where(path: str, quals, project=None,
     join = _check_join(meta, join, pattr)
     if pattr is not None:
         project = None
-    cl = clauses(quals) if (quals or join is None) else []
+    project = name_of(project)
+    cl = _named_clauses(quals) if (quals or join is None) else []
+    meta = _with_exprs(meta, [p.col for c in cl for p in c] + ([project] if project else []))
     base = np.concatenate([[0], np.cumsum(meta.rows)]).astype(np.int64)
     nrows = 0
     ids, vals, valid = [], [], []
@@ -1888,7 +2095,8 @@ def host_scan_where(path: str, quals, project=None,
             else:
                 vals.append(np.asarray(v)[sel])
             valid.append(ok[sel] if ok is not None else np.ones(len(sel), bool))
-    out = HostScanOut(nrows, np.concatenate(ids) if ids else np.zeros(0, np.int64))
+    out = HostScanOut(nrows, np.concatenate(ids) if ids else np.zeros(0, np.int64),
+                      exprs=list(getattr(meta, "progs", {}).values()))
     if pattr is not None:
         out.dictionary = pattr.values
     if project or pattr is not None:
@@ -1936,6 +2144,7 @@ class _AggSpec:
     hash_unsigned: bool = False             # its keys are uint64
     keyspec: Optional[G.KeySpec] = None     # by=HashBy([...]): how the components are packed
     key_attrs: Optional[list] = None        # per component: a join attribute's values, or None
+    exprs: list = field(default_factory=list)   # the query's computed columns (Programs)
 
 
 def _check_range(spec: G.KeySpec, misfit) -> None:
@@ -2071,6 +2280,7 @@ def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary,
         # matched, so the null slot stays empty (the kernels want two slots)
         keyvals, key_code = list(jattr.values), COL_CODE["i4"]
         nslots = max(len(keyvals), 1) + 1
+    exprs = list(getattr(meta, "progs", {}).values())
     entries = [A.Entry(A.COUNT | A.ALL)]
     entry_names: List[Optional[str]] = [None]
     for col, o in ops.items():
@@ -2086,10 +2296,11 @@ def _agg_spec(meta: ArrowFile, aggs, by: Optional[str], dictionary,
         return _AggSpec(aggs, hb.col, A.Layout(entries), entry_names, names,
                         {n: schema[n] for n in names}, None, hashed=True,
                         hash_unsigned=keyspec is not None or schema[hb.col].storage[0] == "u",
-                        keyspec=keyspec, key_attrs=key_attrs)
+                        keyspec=keyspec, key_attrs=key_attrs, exprs=exprs)
     return _AggSpec(aggs, by if jattr is None else jattr.name,
                     A.Layout(entries, nslots, key_code), entry_names, names,
-                    {n: schema[n] for n in names}, keyvals, join_attr=jattr is not None)
+                    {n: schema[n] for n in names}, keyvals, join_attr=jattr is not None,
+                    exprs=exprs)
 
 
 @dataclass
@@ -2127,9 +2338,16 @@ class AggOut:
     # None for a null.  None for every other by=
     key_columns: Optional[List[Tuple[np.ndarray, np.ndarray]]] = None
 
+    @property
+    def exprs(self) -> list:
+        """The computed columns of the query (ops/colexpr.Program), each
+        distinct expression once."""
+        return self._spec.exprs if self._spec is not None else []
+
     def get(self, fn: str, col: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray]:
-        """(values, valid) of one requested aggregate."""
-        i = self.aggs.index((fn, col))
+        """(values, valid) of one requested aggregate (``col``: the name
+        or the expression it was asked with)."""
+        i = self.aggs.index((fn, name_of(col)))
         return self.values[i], self.valid[i]
 
     def merge(self, other: "AggOut") -> "AggOut":
@@ -2259,12 +2477,13 @@ def host_aggregate(path: str, quals, aggs, by=None,
     t0 = time.perf_counter()
     meta = meta if meta is not None else read_metadata(path)
     dicts = dicts if dicts is not None else {}
-    cl = clauses(quals) if quals else []
+    cl = _named_clauses(quals) if quals else []
     battr = by if isinstance(by, JoinAttr) else None
     hb = by if isinstance(by, HashBy) else None
     join = _check_join(meta, join, battr if hb is None else hb.attrs)
     if battr is not None or hb is not None:
         by = None
+    aggs, meta = _agg_exprs(meta, cl, aggs, by, hb)
     spec = _agg_spec(meta, aggs, by, lambda name: _dictionary(meta, path, dicts, name), battr, hb)
     found = G.empty_groups(spec.layout.entries, spec.hash_unsigned, spec.keyspec) \
         if hb is not None else None
@@ -2331,6 +2550,7 @@ class _TopSpec:
     pnullable: bool = False
     pattr: bool = False
     dictionary: object = None
+    exprs: list = field(default_factory=list)   # the query's computed columns (Programs)
 
     def same(self, o: "_TopSpec") -> bool:
         return (self.order_by, self.k, self.descending, self.project, self.pattr) == \
@@ -2360,7 +2580,8 @@ def _top_spec(meta: ArrowFile, order_by: str, k: int, descending: bool, project:
         raise NotImplementedError(f"ORDER BY {order_by}: {kind} columns are not ordered on the "
                                   "GPU (integer, float32/64, date, time, timestamp and duration "
                                   "columns are)")
-    out = _TopSpec(order_by, k, bool(descending), c, _file_nulls(meta, order_by))
+    out = _TopSpec(order_by, k, bool(descending), c, _file_nulls(meta, order_by),
+                   exprs=list(getattr(meta, "progs", {}).values()))
     if pattr is not None:
         out.project, out.pattr, out.dictionary = pattr.name, True, pattr.values
     elif project is not None:
@@ -2406,6 +2627,11 @@ class TopOut:
     _spec: Optional[_TopSpec] = None
     _entries: Optional[np.ndarray] = None   # the candidates (ops/coltopk.py)
 
+    @property
+    def exprs(self) -> list:
+        """The computed columns of the query (ops/colexpr.Program)."""
+        return self._spec.exprs if self._spec is not None else []
+
     def merge(self, other: "TopOut") -> "TopOut":
         """The ``k`` best of this result and another of the same query over
         other record batches of the same file (another rank), on the host."""
@@ -2449,9 +2675,12 @@ def host_top(path: str, quals, order_by: str, k: int, descending: bool = False, 
     join = _check_join(meta, join, pattr)
     if pattr is not None:
         project = None
+    order_by, project = _order_name(order_by), name_of(project)
+    cl = _named_clauses(quals) if quals else []
+    meta = _with_exprs(meta, [p.col for c in cl for p in c] + [order_by] +
+                       ([project] if project else []))
     spec = _top_spec(meta, order_by, k, descending, project, pattr,
                      lambda name: _dictionary(meta, path, dicts, name))
-    cl = clauses(quals) if quals else []
     base = np.concatenate([[0], np.cumsum(meta.rows)]).astype(np.int64)
     ent = np.zeros((0, T.ENTRY_WORDS), np.uint64)
     nrows = selected = 0

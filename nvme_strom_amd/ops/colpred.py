@@ -61,7 +61,7 @@ _NEG = {"!=": "==", "not in": "in", "not prefix": "prefix"}
 
 @dataclass(frozen=True)
 class Pred:
-    col: str
+    col: object                   # a column name, or an expression (ops/colexpr.E)
     op: str
     value: object = None
 
@@ -72,7 +72,8 @@ class Pred:
 
 class P:
     """Builder: ``P("name") == "abc"``, ``P("d").between(a, b)``,
-    ``P("k").isin([1, 5])``, ``P("s").startswith("ab")``."""
+    ``P("k").isin([1, 5])``, ``P("s").startswith("ab")``.  Arithmetic on it
+    gives an expression (ops/colexpr.py): ``P("a") * 2 + P("b") > 5``."""
 
     def __init__(self, col: str):
         self.col = col
@@ -84,6 +85,23 @@ class P:
     def __gt__(self, v): return Pred(self.col, ">", v)       # noqa: E704
     def __ge__(self, v): return Pred(self.col, ">=", v)      # noqa: E704
     __hash__ = None
+
+    def _e(self):
+        from .colexpr import E
+        return E(self.col)
+
+    def __add__(self, o): return self._e() + o               # noqa: E704
+    def __radd__(self, o): return o + self._e()              # noqa: E704
+    def __sub__(self, o): return self._e() - o               # noqa: E704
+    def __rsub__(self, o): return o - self._e()              # noqa: E704
+    def __mul__(self, o): return self._e() * o               # noqa: E704
+    def __rmul__(self, o): return o * self._e()              # noqa: E704
+    def __truediv__(self, o): return self._e() / o           # noqa: E704
+    def __rtruediv__(self, o): return o / self._e()          # noqa: E704
+    def __floordiv__(self, o): return self._e() // o         # noqa: E704
+    def __mod__(self, o): return self._e() % o               # noqa: E704
+    def __neg__(self): return -self._e()                     # noqa: E704
+    def __abs__(self): return abs(self._e())                 # noqa: E704
 
     def between(self, lo, hi) -> Pred:
         return Pred(self.col, "between", (lo, hi))
@@ -120,7 +138,7 @@ class Or:
 def as_pred(q) -> Pred:
     if isinstance(q, Pred):
         return q
-    if isinstance(q, tuple) and len(q) >= 2 and isinstance(q[0], str):
+    if isinstance(q, tuple) and len(q) >= 2 and (isinstance(q[0], str) or hasattr(q[0], "key")):
         if isinstance(q[1], str) and q[1] in OPS:
             return Pred(q[0], q[1], q[2] if len(q) > 2 else None)
         if len(q) == 3:

@@ -571,6 +571,68 @@ def hashagg_row(path: str, fd: int, a, col) -> dict:
     return row
 
 
+def expr_row(path: str, fd: int, a, col) -> dict:
+    """``aggregate([], [sum(E("val") * E("x"))])`` — a computed column
+    (colexpr.hip) aggregated — alternated with ``aggregate([], [sum(val),
+    sum(x)])``: both read and decode the same two columns, so the difference is
+    the expression stage (one launch per group, 8 bytes per row written and
+    read again).  The file is evicted before every run; the sum is verified
+    against numpy within the float-sum bound."""
+    import math
+
+    import torch
+
+    import nvme_strom_amd as S
+    from nvme_strom_amd.models.arrow_scan import ArrowScan
+    from nvme_strom_amd.ops.colexpr import E
+    e = E("val") * E("x")
+    with_e, plain = [("sum", e)], [("sum", "val"), ("sum", "x")]
+    sc = ArrowScan(path, "cuda", slot_bytes=a.slot_mib << 20, nslots=a.nslots or None,
+                   chunk_sz=(a.chunk_kib << 10) or None)
+
+    def timed(fn):
+        S.evict_file(fd)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t, out
+    expr_s, plain_s = [], []
+    try:
+        timed(lambda: sc.aggregate([], with_e))                   # cold: plans, slots, code
+        timed(lambda: sc.aggregate([], plain))
+        for k in range(max(1, a.agg_pairs)):
+            for what in (("expr", "plain") if k % 2 == 0 else ("plain", "expr")):
+                if what == "expr":
+                    dt, out = timed(lambda: sc.aggregate([], with_e))
+                    expr_s.append(dt)
+                else:
+                    dt, flat = timed(lambda: sc.aggregate([], plain))
+                    plain_s.append(dt)
+            _log(f"expr pair {k}: sum(val * x) {expr_s[-1] * 1e3:.1f} ms, sum(val), sum(x) "
+                 f"{plain_s[-1] * 1e3:.1f} ms")
+    finally:
+        sc.close()
+    (vv, vok), (xv, xok) = col("val"), col("x")
+    m = np.ones(len(vv), bool)
+    for okk in (vok, xok):
+        if okk is not None:
+            m &= okk
+    prod = vv[m].astype(np.float64) * xv[m].astype(np.float64)
+    got = float(out.get("sum", e)[0][0])
+    ok = bool(abs(got - math.fsum(prod)) <= len(prod) * 2.0 ** -52 * math.fsum(np.abs(prod)) and
+              out.selected == flat.selected and out.bytes_read == flat.bytes_read)
+    ratios = [x / y for x, y in zip(expr_s, plain_s)]
+    row = dict(aggs=["sum(val * x)"], against=["sum(val)", "sum(x)"], selected=out.selected,
+               verified=ok, bytes_read=out.bytes_read, column_bytes=out.column_bytes,
+               groups=out.groups, expr_ms=[round(x * 1e3, 2) for x in expr_s],
+               plain_ms=[round(x * 1e3, 2) for x in plain_s],
+               median_ratio_expr_over_plain=round(float(np.median(ratios)), 4),
+               expr_breakdown_s={k: round(v, 4) for k, v in out.seconds.items()},
+               column_GBps=round(out.column_bytes / float(np.median(expr_s)) / 1e9, 2))
+    _log(json.dumps(row))
+    return row
+
+
 def topk_rows(path: str, fd: int, a, col) -> dict:
     """ORDER BY ... LIMIT k rows: ``top val k=100`` (the ``val`` row's range
     as qualifier, ORDER BY val LIMIT 100), the same under qual2's two-column
@@ -769,6 +831,9 @@ def main(argv=None) -> int:
                     help="add the ORDER BY ... LIMIT k rows: ArrowScan.top alternated with "
                          "scan_where of the same qualifier list (--topk-pairs pairs)")
     ap.add_argument("--topk-pairs", type=int, default=4)
+    ap.add_argument("--expr", action="store_true",
+                    help="add the computed-column row: aggregate sum(E(val) * E(x)) alternated "
+                         "with aggregate sum(val), sum(x) (--agg-pairs pairs)")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     import torch
@@ -884,6 +949,8 @@ def main(argv=None) -> int:
             res["hashagg"] = hashagg_row(path, fd, a, col)
         if a.topk:
             res["topk"] = topk_rows(path, fd, a, col)
+        if a.expr:
+            res["expr"] = expr_row(path, fd, a, col)
     finally:
         os.close(fd)
     if a.hashagg:
@@ -940,7 +1007,8 @@ def main(argv=None) -> int:
         all(r["verified"] for r in res.get("join", {}).values()) and \
         all(r["verified"] for r in res.get("topk", {}).values()) and \
         res.get("hashagg", {}).get("verified", True) and \
-        res.get("hashagg2", {}).get("verified", True)
+        res.get("hashagg2", {}).get("verified", True) and \
+        res.get("expr", {}).get("verified", True)
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:

@@ -39,7 +39,8 @@ def main(argv=None):
                          "join (hash-join probe next to column_filter_i64), "
                          "join_star (star probe of 2-4 legs next to the chained probes), "
                          "hashagg (hash GROUP BY next to column_filter_i64 and the LDS path), "
-                         "topk (ORDER BY ... LIMIT k select + merge next to column_filter_i64)")
+                         "topk (ORDER BY ... LIMIT k select + merge next to column_filter_i64), "
+                         "expr (computed columns next to column_filter_i64)")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     only = set(a.only.split(","))
@@ -193,6 +194,8 @@ def main(argv=None):
         _hashagg_rows(n, dev, log, column_filter)
     if "topk" in only:
         _topk_rows(n, dev, log, column_filter)
+    if "expr" in only:
+        _expr_rows(n, dev, log, column_filter)
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:
@@ -385,6 +388,53 @@ def _topk_rows(n, dev, log, column_filter):
                     assert np.array_equal(vals, want.cpu().numpy()), (st, shape, k, sel)
                     assert np.array_equal(col[torch.from_numpy(rows).to(dev)].cpu().numpy(), vals)
             del col, tab
+
+
+def _expr_rows(n, dev, log, column_filter):
+    """Computed columns (colexpr.hip) alone on one HBM-resident record batch,
+    next to column_filter_i64 of the same run: one and three source columns,
+    int64 and float64, without a selection, with every word selected and with
+    nine words of ten skipped.  GB/s of the bytes a launch moves: 8 per source
+    row in and 8 out, for the rows of the words it evaluates.  Each row's
+    result is checked against torch."""
+    from nvme_strom_amd.ops import colexpr as X
+    from nvme_strom_amd.utils.arrow_ipc import Column
+    nv = n // 8 // 4                       # three sources and the result: n bytes in all
+    nwords = (nv + 63) // 64
+    v = torch.randint(-1000, 1000, (nv,), dtype=torch.int64, device=dev)
+    log("column_filter_i64", timed(lambda: column_filter(v, -100, 100), 20), nv * 8)
+    ints = [v, torch.randint(-1000, 1000, (nv,), dtype=torch.int64, device=dev),
+            torch.randint(1, 1000, (nv,), dtype=torch.int64, device=dev)]
+    flts = [torch.rand(nv, dtype=torch.float64, device=dev) for _ in range(3)]
+    E = X.E
+    rows = (("i64_1col", E("a") * 3 + 1, ints, lambda a, b, c: a * 3 + 1),
+            ("i64_3col", E("a") * E("b") + E("c"), ints, lambda a, b, c: a * b + c),
+            ("i64_3col_floor", (E("a") * E("b")) // 7 + E("c") % 5, ints,
+             lambda a, b, c: torch.div(a * b, 7, rounding_mode="floor") + torch.remainder(c, 5)),
+            ("f64_1col", E("a") * 0.5 + 1.0, flts, lambda a, b, c: a * 0.5 + 1.0),
+            ("f64_3col", E("a") * (1.0 - E("b")) + E("c"), flts, lambda a, b, c: a * (1.0 - b) + c),
+            ("f64_3col_div", E("a") / (E("b") + 1.0) - E("c"), flts,
+             lambda a, b, c: a / (b + 1.0) - c))
+    tenth = torch.zeros(nwords, dtype=torch.int64, device=dev)
+    tenth[::10] = -1
+    sels = {"none": (None, 1.0), "all": (torch.full((nwords,), -1, dtype=torch.int64, device=dev),
+                                         1.0), "tenth": (tenth, 0.1)}
+    out = torch.empty(nwords * 64, dtype=torch.int64, device=dev)
+    okw = torch.empty(nwords, dtype=torch.int64, device=dev)
+    otab = torch.tensor([[out.data_ptr(), okw.data_ptr(), nv, 0, 0]], dtype=torch.int64, device=dev)
+    for name, e, cols, ref in rows:
+        flt = cols is flts
+        sch = [Column(c, "float" if flt else "int", 64) for c in "abc"]
+        prog = X.compile_expr(e, sch)
+        stab = torch.tensor([[[cols["abc".index(c)].data_ptr(), 0, nv, 0, 0]]
+                             for c in prog.columns], dtype=torch.int64, device=dev)
+        for tag, (sel, part) in sels.items():
+            log(f"column_expr_{name}_sel{tag}",
+                timed(lambda: X.expr_batched(prog, stab, nwords, otab, sel), 20),
+                int(part * nv * 8 * (len(prog.columns) + 1)))
+        X.expr_batched(prog, stab, nwords, otab, None)
+        got = out[:nv].view(torch.float64) if flt else out[:nv]
+        assert torch.equal(got, ref(*cols)), name
 
 
 def _hashagg_rows(n, dev, log, column_filter):

@@ -309,11 +309,15 @@ extern "C" int strom_crc32c_chunks(const void *d_in, uint64_t nbytes, uint32_t c
   if (nbytes == 0) return 0;
   uint64_t nch = (nbytes + chunk - 1) / chunk;
   if (nch > 0xffffffffull) return -22;
-  static bool attr_set = false;
-  if (!attr_set) {
+  // the attribute belongs to the current device's copy of the kernel: once
+  // per device, not once per process
+  static bool attr_set[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return -5;
+  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
     (void)hipFuncSetAttribute((const void *)crc32c_chunks_kernel,
                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsWords * 4);
-    attr_set = true;
+    if (dev >= 0 && dev < 64) attr_set[dev] = true;
   }
   // one workgroup per CU holds the 128 KiB tables.  Enough chunks for 8+
   // waves per CU: one wave per chunk, up to 16 waves per workgroup; fewer,

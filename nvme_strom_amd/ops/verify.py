@@ -23,6 +23,8 @@ def crc32c_chunks(buf: torch.Tensor, chunk: int, nbytes: int | None = None,
     nch = (n + chunk - 1) // chunk
     if out is None:
         out = torch.empty(nch, dtype=torch.int32, device=buf.device)
+    if nch == 0:
+        return out          # no bytes, no chunks: an empty tensor has no address to pass
     check(lib().strom_crc32c_chunks(ptr(buf), n, chunk, ptr(out), stream_handle(stream)),
           "crc32c_chunks")
     return out

@@ -595,8 +595,36 @@ int strom_bitmap_to_rows_proj(const uint64_t *d_bitmap, uint64_t nwords,
 #define STROM_QOP_STR_RANGES 6 /* bytewise-lexicographic ranges: per range two bounds of
                                   (start, len, mode) in offs, mode 0 unbounded,
                                   1 inclusive, 2 exclusive */
+#define STROM_QOP_STR_LIKE 7   /* SQL LIKE: the string matches one of nconst patterns
+                                  (csrc/kernels/collike.hip).  A pattern is its segments,
+                                  the pieces between '%'; a segment is literal pieces with
+                                  runs of '_' before and after them.  consts: the literal
+                                  bytes, every piece starting 4-aligned.  offs, uint32 words:
+                                    offs[k], k < nconst: word index of pattern k's record
+                                    pattern: flags (STROM_LIKE_HEAD | STROM_LIKE_TAIL),
+                                             least bytes of a match, nseg,
+                                             then nseg word indexes of segment records
+                                    segment: least bytes, npiece, '_' after the last piece,
+                                             then npiece x ('_' before it, start in
+                                             consts, length > 0)
+                                  With HEAD the first segment starts at the row's first
+                                  byte, with TAIL the last one ends at its last; no segment
+                                  and both flags: only the empty string; no segment and no
+                                  flag: every row. */
+#define STROM_LIKE_HEAD 1
+#define STROM_LIKE_TAIL 2
 #define STROM_QUAL_NEGATE 1    /* NOT of the comparison (still false for nulls) */
 #define STROM_QUAL_NAN 2       /* floats: NaN also matches (IN-lists holding NaN) */
+#define STROM_QUAL_LIKE_WILD 4 /* STR_LIKE: some segment holds a '_' (without it the
+                                  kernel runs its pure byte-search instantiation) */
+#define STROM_QUAL_LIKE_UTF8 8 /* STR_LIKE: '_' is one code point, a byte and every
+                                  0x80-0xBF byte directly after it (else one byte) */
+/* STR_LIKE: a row with more than this many bytes to search for a pattern's
+ * middle segments (a long row, less what the anchored head and tail took) is
+ * matched one row per wave, the 64 lanes testing 64 candidate positions of a
+ * searched segment, instead of one row per lane (STROM_LIKE_LONG_ROW in the
+ * environment overrides it: the knob of tools/kbench.py) */
+#define STROM_LIKE_LONG_ROW 256
 struct strom_col_qual {
 	int32_t type;
 	int32_t op;
@@ -626,6 +654,15 @@ struct strom_qual_batch {
 int strom_column_qual(const struct strom_col_qual *q, const struct strom_qual_batch *d_batches,
                       uint32_t nbatches, uint64_t nwords, uint64_t *d_bitmap,
                       const uint64_t *d_or, int and_dst, uint64_t *d_count, void *stream);
+/* STROM_QOP_STR_LIKE of strom_column_qual on the CPU: the same row matcher
+ * over host pointers (q->consts, q->offs and the batches' buffers in host
+ * memory; the operands are checked, -22 for a record outside offs or a piece
+ * outside consts).  As on the device the character buffer is read in aligned
+ * dwords, so it is 4-byte aligned and readable up to the dword that holds
+ * its last byte. */
+int strom_column_like_host(const struct strom_col_qual *q, const struct strom_qual_batch *batches,
+                           uint32_t nbatches, uint64_t nwords, uint64_t *bitmap,
+                           const uint64_t *or_src, int and_dst, uint64_t *count);
 /* bitmap_to_rows with a utf8/binary column projected (d_strtab: its
  * strom_qual_batch rows, offsets of owidth 4 or 8 bytes): each selected row's
  * characters are appended at the device cursor *d_char_cursor in d_pchars,

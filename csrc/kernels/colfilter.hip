@@ -896,6 +896,12 @@ extern "C" int strom_bitmap_to_rows(const uint64_t *d_bitmap, uint64_t nwords,
                                    0, nullptr, nullptr, stream);
 }
 
+// collike.hip
+extern "C" int strom_column_like(const strom_col_qual *q, const strom_qual_batch *d_batches,
+                                 uint32_t nbatches, uint64_t nwords, uint64_t *d_bitmap,
+                                 const uint64_t *d_or, int and_dst, uint64_t *d_count,
+                                 void *stream);
+
 extern "C" int strom_column_qual(const strom_col_qual *q, const strom_qual_batch *d_batches,
                                  uint32_t nbatches, uint64_t nwords, uint64_t *d_bitmap,
                                  const uint64_t *d_or, int and_dst, uint64_t *d_count,
@@ -934,6 +940,9 @@ extern "C" int strom_column_qual(const strom_col_qual *q, const strom_qual_batch
         return launch_qual<int32_t, QK_STR>(*q, d_batches, nbatches, nwords, d_bitmap, d_or, and_dst, d_count, st);
       return launch_qual<int64_t, QK_STR>(*q, d_batches, nbatches, nwords, d_bitmap, d_or, and_dst, d_count, st);
     }
+    case STROM_QOP_STR_LIKE:   // a search per row, not a compare: its own kernel
+      return strom_column_like(q, d_batches, nbatches, nwords, d_bitmap, d_or, and_dst, d_count,
+                               stream);
     case STROM_QOP_VALID:
       return launch_qual<int32_t, QK_VALID>(*q, d_batches, nbatches, nwords, d_bitmap, d_or, and_dst, d_count, st);
     default:

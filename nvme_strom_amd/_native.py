@@ -335,6 +335,8 @@ _SIGS = {
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "strom_column_qual": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "strom_column_like_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "strom_bitmap_to_rows_str": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

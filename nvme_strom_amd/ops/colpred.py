@@ -13,6 +13,9 @@ A qualifier list is a conjunction (CNF): each item is one predicate or an
         "in" / "not in" [values]        IN-lists (numbers, strings, dates ...)
         "ranges" [(lo, hi), ...]        an OR of inclusive ranges on one column
         "prefix" / "not prefix" s       utf8/binary starts-with (a list: any of)
+        "suffix" / "not suffix" s       ... ends-with (a list: any of)
+        "contains" / "not contains" s   ... holds s somewhere (a list: any of)
+        "like" / "not like" pattern     SQL LIKE, see below
     (name, "is_null") / (name, "is_valid")
 
 Nulls never satisfy a comparison (SQL: a NULL comparison is not true, and
@@ -22,6 +25,22 @@ follow pyarrow.compute: NaN compares false (so ``!=`` selects it) and
 ``in`` matches NaN to a NaN in the list.  Integers compare exactly (bounds
 in the column's own integer domain: ``v < 2.5`` is ``v <= 2``), floats in
 double (pyarrow promotes float32 against a Python float the same way).
+
+LIKE follows pyarrow.compute.match_like: ``%`` matches any run of
+characters (the empty one too), ``_`` exactly one character, a code point on
+a utf8 column and a byte on a binary one, newlines included; ``\\`` escapes
+``%``, ``_`` and itself, and before anything else (or at the end) it is a
+``ValueError``.  The constants of ``contains`` / ``suffix`` are literal; they
+compile to the patterns ``%x%`` / ``%x``, so one kernel
+(csrc/kernels/collike.hip) serves all of them.  A utf8 column may hold bytes
+that are not UTF-8 (file data): there ``_`` is one byte and every 0x80-0xBF
+byte directly after it, in the kernel, its host copy and the twin here
+alike; pyarrow parity holds for valid UTF-8 and for binary columns.  Limits
+(``ValueError`` beyond them): ``MAX_LIKE_BYTES`` bytes per pattern,
+``MAX_LIKE_SEGMENTS`` pieces between ``%`` per pattern, ``MAX_LIKE_PATTERNS``
+patterns per predicate, and all operands within ``MAX_QUAL_BYTES``.  Not
+offered: case-insensitive matching (ILIKE), regular expressions, another
+escape character, collations, ``_`` as a grapheme cluster.
 
 Dictionary-encoded columns are evaluated on the dictionary (host, numpy,
 this module's twin) and the GPU tests each row's index against the
@@ -48,15 +67,23 @@ COL_CODE = {"i4": 1, "i8": 2, "f4": 3, "f8": 4, "i1": 5, "i2": 6, "u1": 7, "u2":
             "u8": 10, "b1": 11, "d16": 14}
 COL_STR32, COL_STR64 = 12, 13
 QOP_RANGES, QOP_STR_IN, QOP_STR_PREFIX, QOP_LUT, QOP_VALID, QOP_STR_RANGES = 1, 2, 3, 4, 5, 6
-FLAG_NEGATE, FLAG_NAN = 1, 2
+QOP_STR_LIKE = 7
+FLAG_NEGATE, FLAG_NAN, FLAG_LIKE_WILD, FLAG_LIKE_UTF8 = 1, 2, 4, 8
+LIKE_HEAD, LIKE_TAIL = 1, 2       # pattern flags: no leading / no trailing %
 MAX_RANGES = 4096                 # the kernel stages constants in LDS (<= 64 KiB)
 MAX_CONST_BYTES = 48 << 10
 MAX_QUAL_BYTES = 64 << 10         # strom_column_qual: constants + string offsets
 MAX_LUT_BITS = 512 << 10
+MAX_LIKE_BYTES = 4096             # one LIKE pattern (a contains / suffix constant)
+MAX_LIKE_SEGMENTS = 64            # its pieces between %
+MAX_LIKE_PATTERNS = 64            # patterns OR-ed in one predicate
 
 OPS = {"==", "!=", "<", "<=", ">", ">=", "between", "in", "not in", "ranges", "prefix",
-       "not prefix", "is_null", "is_valid"}
-_NEG = {"!=": "==", "not in": "in", "not prefix": "prefix"}
+       "not prefix", "suffix", "not suffix", "contains", "not contains", "like", "not like",
+       "is_null", "is_valid"}
+_NEG = {"!=": "==", "not in": "in", "not prefix": "prefix", "not suffix": "suffix",
+        "not contains": "contains", "not like": "like"}
+_LIKE_OPS = ("like", "contains", "suffix")
 
 
 @dataclass(frozen=True)
@@ -118,6 +145,18 @@ class P:
     def startswith(self, prefix) -> Pred:
         return Pred(self.col, "prefix", prefix)
 
+    def endswith(self, suffix) -> Pred:
+        return Pred(self.col, "suffix", suffix)
+
+    def contains(self, sub) -> Pred:
+        return Pred(self.col, "contains", sub)
+
+    def like(self, pattern) -> Pred:
+        return Pred(self.col, "like", pattern)
+
+    def not_like(self, pattern) -> Pred:
+        return Pred(self.col, "not like", pattern)
+
     def is_null(self) -> Pred:
         return Pred(self.col, "is_null")
 
@@ -175,6 +214,7 @@ class Compiled:
     ranges: Optional[np.ndarray] = None       # (n, 2) in the compare domain
     strings: Optional[List[bytes]] = None
     lut: Optional[np.ndarray] = None          # bool per dictionary index
+    patterns: Optional[list] = None           # LIKE: (head, tail, segments) per pattern
     _dev: Dict[str, object] = field(default_factory=dict, repr=False)
 
 
@@ -414,6 +454,111 @@ def _string_ranges(op: str, v, col: Column, code: int, flags: int) -> Compiled:
                     np.asarray(offs, np.uint32).tobytes(), strings=rs)
 
 
+def _like_escape(b: bytes) -> bytes:
+    return b.replace(b"\\", b"\\\\").replace(b"%", b"\\%").replace(b"_", b"\\_")
+
+
+def _like_parse(pat: bytes, col: Column):
+    """(head, tail, segments) of one LIKE pattern.  head / tail: it has no
+    leading / trailing ``%``.  A segment, one of the pieces between ``%``,
+    is (pieces, trail, least): pieces a list of (number of ``_`` before
+    it, literal bytes), trail the ``_`` after the last piece, least the
+    fewest bytes it can match (a ``_`` is at least one byte)."""
+    segs, toks, i, n = [], [], 0, len(pat)       # toks: a byte value, or None for _
+    cuts = 0
+    while i < n:
+        ch = pat[i]
+        if ch == 0x5C:                             # backslash
+            if i + 1 >= n or pat[i + 1] not in b"%_\\":
+                raise ValueError(f"column {col.name}: LIKE pattern {pat!r}: a backslash escapes "
+                                 f"only %, _ and itself (at byte {i})")
+            toks.append(pat[i + 1])
+            i += 2
+            continue
+        if ch == 0x25:                             # %
+            segs.append(toks)
+            toks = []
+            cuts += 1
+        else:
+            toks.append(None if ch == 0x5F else ch)
+        i += 1
+    segs.append(toks)
+    head, tail = bool(segs[0]) or not cuts, bool(segs[-1]) or not cuts
+    out = []
+    for toks in segs:
+        if not toks:
+            continue
+        pieces, skip, lit = [], 0, bytearray()
+        for t in toks:
+            if t is None:
+                if lit:
+                    pieces.append((skip, bytes(lit)))
+                    skip, lit = 0, bytearray()
+                skip += 1
+            else:
+                lit.append(t)
+        trail = 0
+        if lit:
+            pieces.append((skip, bytes(lit)))
+        else:
+            trail = skip
+        out.append((pieces, trail, len(toks)))
+    return head, tail, out
+
+
+def _compile_like(op: str, v, col: Column, code: int, flags: int) -> Compiled:
+    """``like`` / ``contains`` / ``suffix`` to the STROM_QOP_STR_LIKE
+    operands (strom.h has the layout): the literal pieces 4-aligned in
+    ``consts``; in ``offs`` one word per pattern (where its record is),
+    then the pattern records (flags, least bytes, nseg, where each segment
+    record is) and the segment records (least bytes, npiece, trailing
+    ``_``, then per piece: ``_`` before it, start, length)."""
+    if op == "like":
+        if isinstance(v, (list, tuple)):
+            raise ValueError(f"column {col.name}: like takes one pattern")
+        pats = [_string_const(v, col)]
+    else:
+        vs = v if isinstance(v, (list, tuple)) else [v]
+        wrap = (b"%", b"%") if op == "contains" else (b"%", b"")
+        pats = [wrap[0] + _like_escape(_string_const(x, col)) + wrap[1] for x in vs]
+    pats = sorted(set(pats))
+    if not pats or len(pats) > MAX_LIKE_PATTERNS:
+        raise ValueError(f"column {col.name}: {len(pats)} patterns in one predicate "
+                         f"(1 to MAX_LIKE_PATTERNS = {MAX_LIKE_PATTERNS})")
+    parsed = []
+    for pat in pats:
+        if len(pat) > MAX_LIKE_BYTES:
+            raise ValueError(f"column {col.name}: a pattern of {len(pat)} bytes "
+                             f"(MAX_LIKE_BYTES = {MAX_LIKE_BYTES})")
+        head, tail, segs = _like_parse(pat, col)
+        if len(segs) > MAX_LIKE_SEGMENTS:
+            raise ValueError(f"column {col.name}: {len(segs)} segments between % in one pattern "
+                             f"(MAX_LIKE_SEGMENTS = {MAX_LIKE_SEGMENTS})")
+        parsed.append((head, tail, segs))
+    blob, words = bytearray(), [0] * len(parsed)
+    wild = False
+    for k, (head, tail, segs) in enumerate(parsed):
+        words[k] = len(words)
+        at = len(words)
+        words += [(LIKE_HEAD if head else 0) | (LIKE_TAIL if tail else 0),
+                  sum(s[2] for s in segs), len(segs)] + [0] * len(segs)
+        for j, (pieces, trail, least) in enumerate(segs):
+            words[at + 3 + j] = len(words)
+            words += [least, len(pieces), trail]
+            wild |= bool(trail) or any(sk for sk, _ in pieces)
+            for sk, lit in pieces:
+                words += [sk, len(blob), len(lit)]
+                blob += lit + b"\0" * (-len(lit) % 4)
+    if len(blob) + 4 * len(words) > MAX_QUAL_BYTES:
+        raise ValueError(f"column {col.name}: LIKE operands of {len(blob) + 4 * len(words)} bytes "
+                         f"(MAX_QUAL_BYTES = {MAX_QUAL_BYTES}: literals, 12 bytes per piece, "
+                         f"16 per segment and per pattern)")
+    if wild:
+        flags |= FLAG_LIKE_WILD | (FLAG_LIKE_UTF8 if col.kind == "utf8" else 0)
+    return Compiled(code, QOP_STR_LIKE, flags, len(parsed), bytes(blob) or b"\0\0\0\0",
+                    np.asarray(words, np.uint32).tobytes(), patterns=parsed)
+
+
 def _compile_value(p: Pred, col: Column, dt: str, code: int) -> Compiled:
     """A predicate on a plain (not dictionary-encoded) column."""
     op = p.op
@@ -423,6 +568,8 @@ def _compile_value(p: Pred, col: Column, dt: str, code: int) -> Compiled:
         return Compiled(code, QOP_VALID, FLAG_NEGATE if base == "is_null" else 0)
     flags = FLAG_NEGATE if neg else 0
     if col.kind in ("utf8", "binary"):
+        if base in _LIKE_OPS:
+            return _compile_like(base, p.value, col, code, flags)
         if base == "==":
             vals, qop = [_string_const(p.value, col)], QOP_STR_IN
         elif base == "in":
@@ -444,8 +591,8 @@ def _compile_value(p: Pred, col: Column, dt: str, code: int) -> Compiled:
                              f"{MAX_QUAL_BYTES} with 8 per constant)")
         return Compiled(code, qop, flags, len(vals), bytes(blob) or b"\0\0\0\0",
                         np.asarray(offs or [0, 0], np.uint32).tobytes(), strings=vals)
-    if base == "prefix":
-        raise ValueError(f"column {col.name} ({col.kind}): prefix needs utf8/binary")
+    if base == "prefix" or base in _LIKE_OPS:
+        raise ValueError(f"column {col.name} ({col.kind}): {base} needs utf8/binary")
     rs, extra = _num_ranges(base, p.value, col, dt)
     limit = min(MAX_RANGES, MAX_QUAL_BYTES // (32 if dt == "d16" else 16))
     if len(rs) > limit:
@@ -512,6 +659,134 @@ def _str_rows(values, n: int, ok: np.ndarray):
     return np.where(bad, 0, a), np.where(bad, 0, e - a), data, ok & ~bad
 
 
+# LIKE: the kernel's segment algorithm (csrc/kernels/collike.hip), every step
+# one numpy operation over the rows (or candidate positions) still matching;
+# the Python loops run over a pattern's segments, pieces and bytes only.
+def _like_fwd(seg, p, lim, data, nxt, want_need: bool = False):
+    """The segment at positions ``p``, each inside [p, lim): (matches, where
+    it ends[, need]).  ``nxt``: per position the next one that continues no
+    character (utf8), None for one byte per ``_``.  ``need``: the end, or
+    with a trailing ``_`` one byte past where the last ``_`` starts - a match
+    found with a limit further out holds for a nearer limit iff need <= it,
+    and then ends at min(end, limit): only the last ``_`` can be cut short."""
+    pieces, trail, _ = seg
+    q = np.array(p, np.int64)
+    alive = np.arange(len(q))
+
+    def skip(alive, k):
+        for _ in range(k):
+            alive = alive[q[alive] < lim[alive]]
+            a = q[alive]
+            q[alive] = a + 1 if nxt is None else np.minimum(nxt[a], lim[alive])
+        return alive
+    for sk, lit in pieces:
+        alive = skip(alive, sk)
+        alive = alive[lim[alive] - q[alive] >= len(lit)]
+        for j, ch in enumerate(lit):
+            alive = alive[data[q[alive] + j] == ch]
+        q[alive] += len(lit)
+    need = None
+    if trail:
+        alive = skip(alive, trail - 1)
+        alive = alive[q[alive] < lim[alive]]
+        need = q + 1
+        alive = skip(alive, 1)
+    ok = np.zeros(len(q), bool)
+    ok[alive] = True
+    if want_need:
+        return ok, q, (q if need is None else need)
+    return ok, q
+
+
+def _like_bwd(seg, e, lo, data, prv):
+    """The segment ending at positions ``e``, each inside [lo, e): (matches,
+    where it begins).  ``prv``: per position the last one before it that
+    continues no character (-1: none), None for one byte per ``_``."""
+    pieces, trail, _ = seg
+    q = np.array(e, np.int64)
+    alive = np.arange(len(q))
+
+    def skip(alive, k):
+        for _ in range(k):
+            alive = alive[q[alive] > lo[alive]]
+            a = q[alive]
+            q[alive] = a - 1 if prv is None else np.maximum(prv[a], lo[alive])
+        return alive
+    alive = skip(alive, trail)
+    for sk, lit in reversed(pieces):
+        L = len(lit)
+        alive = alive[q[alive] - lo[alive] >= L]
+        for j, ch in enumerate(lit):
+            alive = alive[data[q[alive] - L + j] == ch]
+        q[alive] -= L
+        alive = skip(alive, sk)
+    ok = np.zeros(len(q), bool)
+    ok[alive] = True
+    return ok, q
+
+
+def _like_scan(seg, data, nxt):
+    """Every position of the character buffer the segment matches at,
+    ascending, with (need, end) of each match as _like_fwd defines them for
+    the buffer's end as the limit."""
+    N = len(data)
+    pieces = seg[0]
+    if pieces and not pieces[0][0]:                 # starts with a literal: its first byte
+        L = len(pieces[0][1])
+        p = np.flatnonzero(data[:max(N - L + 1, 0)] == pieces[0][1][0])
+    else:
+        p = np.arange(N + 1)
+    ok, q, need = _like_fwd(seg, p, np.full(len(p), N, np.int64), data, nxt, True)
+    return p[ok], need[ok], q[ok]
+
+
+def _like_eval(c: Compiled, st, ln, data) -> np.ndarray:
+    n, N = len(st), len(data)
+    hit = np.zeros(n, bool)
+    nxt = prv = None
+    if c.flags & FLAG_LIKE_UTF8:
+        lead = np.flatnonzero((data & 0xC0) != 0x80)
+        at = np.arange(N + 1)
+        nxt = np.concatenate([lead, [N]])[np.searchsorted(lead, at, side="right")]
+        prv = np.concatenate([[-1], lead])[np.searchsorted(lead, at, side="left")]
+    en = st + ln
+    for head, tail, segs in c.patterns:
+        rows = np.flatnonzero(~hit & (ln >= sum(s[2] for s in segs)))   # the length reject
+        if not segs:
+            hit[rows[ln[rows] == 0] if head else rows] = True
+            continue
+        cur, end = st[rows].astype(np.int64), en[rows].astype(np.int64)
+        first, last = 0, len(segs)
+        if head:
+            ok, q = _like_fwd(segs[0], cur, end, data, nxt)
+            if tail and len(segs) == 1:
+                hit[rows[ok & (q == end)]] = True
+                continue
+            first = 1
+            rows, cur, end = rows[ok], q[ok], end[ok]
+        if tail:
+            # from the end, and not beginning before the point the head ended at
+            ok, q = _like_bwd(segs[-1], end, cur, data, prv)
+            last -= 1
+            rows, cur, end = rows[ok], cur[ok], q[ok]
+        # the segments between, leftmost-first.  No backtracking across a %:
+        # where a segment can end never decreases with where it starts, so
+        # the leftmost match leaves the longest remainder for the rest.
+        for seg in segs[first:last]:
+            if not len(rows):
+                break
+            pos, need, e = _like_scan(seg, data, nxt)
+            if not len(pos):
+                rows = rows[:0]
+                break
+            j = np.searchsorted(pos, cur)
+            jj = np.minimum(j, len(pos) - 1)
+            ok = (j < len(pos)) & (need[jj] <= end)
+            rows, cur, end = rows[ok], np.minimum(e[jj], end)[ok], end[ok]
+        hit[rows] = True
+    return hit
+
+
 def evaluate(c: Compiled, values, valid: Optional[np.ndarray], n: int) -> np.ndarray:
     """The kernel's bits for n rows on the host: values as
     arrow_ipc.decode_values returns them (indices for a LUT)."""
@@ -565,6 +840,9 @@ def evaluate(c: Compiled, values, valid: Optional[np.ndarray], n: int) -> np.nda
             ok_lo = [True] * n if not lm else [x >= lo if lm == 1 else x > lo for x in col]
             ok_hi = [True] * n if not hm else [x <= hi if hm == 1 else x < hi for x in col]
             hit |= np.asarray(ok_lo, bool) & np.asarray(ok_hi, bool)
+    elif c.op == QOP_STR_LIKE:
+        st, ln, data, ok = _str_rows(values, n, ok)
+        hit = _like_eval(c, st, ln, data)
     elif c.op == QOP_LUT:
         idx = np.asarray(values[:n]).astype(np.int64)
         inr = (idx >= 0) & (idx < len(c.lut))
@@ -601,6 +879,33 @@ def device_qual(c: Compiled, device) -> ColQual:
                     len(c.consts), len(c.offs))
         c._dev[key] = (q, cs, of)
     return c._dev[key][0]
+
+
+def like_host(c: Compiled, batches: np.ndarray, nwords: int, bitmap: np.ndarray,
+              or_src: Optional[np.ndarray] = None, and_dst: bool = False) -> int:
+    """The library's host copy of the LIKE kernel (strom_column_like_host)
+    over a (nbatches, 7) uint64 table of host pointers: ``bitmap`` (uint64,
+    nwords) is combined as the kernel does; returns the popcount of what was
+    written.  Character buffers are 4-byte aligned and readable up to the
+    dword holding their last byte (numpy allocations padded to 4 are)."""
+    from .. import _native as N
+    if c.op != QOP_STR_LIKE:
+        raise ValueError("like_host: a LIKE predicate")
+    batches = np.ascontiguousarray(batches, np.uint64)
+    if batches.ndim != 2 or batches.shape[1] != QUAL_BATCH_FIELDS or bitmap.dtype != np.uint64 \
+            or len(bitmap) < nwords:
+        raise ValueError("like_host: batches uint64 (n, 7), bitmap uint64[nwords]")
+    cs = np.frombuffer(c.consts, np.uint8).copy()
+    of = np.frombuffer(c.offs, np.uint8).copy()
+    q = ColQual(c.type, c.op, c.flags, c.nconst, cs.ctypes.data, of.ctypes.data, len(cs), len(of))
+    cnt = np.zeros(1, np.uint64)
+    rc = N.lib().strom_column_like_host(C.byref(q), batches.ctypes.data, len(batches), nwords,
+                                        bitmap.ctypes.data,
+                                        or_src.ctypes.data if or_src is not None else None,
+                                        int(and_dst), cnt.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"column_like_host failed (rc={rc})")
+    return int(cnt[0])
 
 
 def qual_batched(c: Compiled, batches, nwords: int, bitmap, count, stream=None,

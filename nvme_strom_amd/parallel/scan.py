@@ -138,8 +138,12 @@ class DistributedArrowScan:
         if gather not in ("all", "none"):
             raise ValueError(f"gather {gather!r}")
         t0 = time.perf_counter()
+        # every spelling of a qualifier list (tuples, P(...) predicates, Or)
+        from ..ops.colpred import clauses
+        cols = [p.col for c in (clauses(quals) if quals else []) for p in c]
         names: List[str] = []
-        for n in [q[0] for q in quals] + ([project] if project else []):
+        for n in [x for c in cols for x in (c.columns() if hasattr(c, "columns") else [c])] + \
+                ([project] if project else []):
             if n not in names:
                 names.append(n)
         rngs = self.ranges(names)

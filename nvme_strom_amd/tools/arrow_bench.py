@@ -27,7 +27,8 @@ against numpy.
 ``--strings`` (default on) adds a second file (``--string-rows``) with a
 utf8 ``name`` column (words of 3-24 bytes), a dictionary-encoded ``cat``
 (1000 categories), a date32 ``day`` and a timestamp ``ts``, and rows for a
-string-equality scan, a string prefix, a dictionary equality, a dictionary
+string-equality scan, a string prefix, contains, suffix and LIKE
+(``str_contains`` / ``str_suffix`` / ``str_like``), a dictionary equality, a dictionary
 range, and a date range AND an OR of timestamp ranges — each verified
 against pyarrow.compute (row ids of Table.filter of the same expression),
 whose time on the memory-mapped file is ``cpu_ms``.
@@ -160,7 +161,10 @@ def pc_expr(quals):
                 "<=": lambda: f <= v, ">": lambda: f > v, ">=": lambda: f >= v,
                 "between": lambda: (f >= v[0]) & (f <= v[1]),
                 "in": lambda: f.isin(list(v)),
-                "prefix": lambda: pc.starts_with(f, pattern=v)}[p.op]()
+                "prefix": lambda: pc.starts_with(f, pattern=v),
+                "contains": lambda: pc.match_substring(f, pattern=v),
+                "suffix": lambda: pc.ends_with(f, pattern=v),
+                "like": lambda: pc.match_like(f, pattern=v)}[p.op]()
     e = None
     for q in quals:
         c = None
@@ -978,6 +982,9 @@ def main(argv=None) -> int:
         sspecs = [
             ("str_eq", [P("name") == word], None),
             ("str_prefix", [P("name").startswith("ab")], None),
+            ("str_contains", [P("name").contains("abc")], None),
+            ("str_suffix", [P("name").endswith("ab")], None),
+            ("str_like", [P("name").like("a%b_c%")], None),
             ("dict_eq", [P("cat") == "cat_00042"], "sid"),
             ("dict_range", [P("cat").between("cat_00100", "cat_00199")], None),
             ("date_ts", [P("day").between(_dt.date(2020, 1, 1), _dt.date(2021, 6, 30)),

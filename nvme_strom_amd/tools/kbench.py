@@ -40,7 +40,9 @@ def main(argv=None):
                          "join_star (star probe of 2-4 legs next to the chained probes), "
                          "hashagg (hash GROUP BY next to column_filter_i64 and the LDS path), "
                          "topk (ORDER BY ... LIMIT k select + merge next to column_filter_i64), "
-                         "expr (computed columns next to column_filter_i64)")
+                         "expr (computed columns next to column_filter_i64), "
+                         "like (column_qual_like: LIKE / contains / endswith next to the string "
+                         "equality and prefix qualifiers, short words and long rows)")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     only = set(a.only.split(","))
@@ -196,11 +198,74 @@ def main(argv=None):
         _topk_rows(n, dev, log, column_filter)
     if "expr" in only:
         _expr_rows(n, dev, log, column_filter)
+    if "like" in only:
+        _like_rows(n, dev, log)
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:
             f.write(js)
     print(js)
+
+
+def _like_rows(n, dev, log):
+    """column_qual_like: the LIKE kernel (collike.hip) on a utf8 column of
+    short words (3-24 random letters, the vocabulary of arrow_bench's string
+    file) and on one of 200-2,000-byte rows, next to the string equality and
+    prefix qualifiers (colfilter.hip) on the same words.  GB/s counts the
+    column's data, offsets + characters.  The long-row rows carry the
+    threshold in their name: run again with STROM_LIKE_LONG_ROW set past
+    every row's length for the row-per-lane path alone."""
+    from nvme_strom_amd.ops import colpred as CP
+    from nvme_strom_amd.utils.arrow_ipc import Column
+    col = Column("name", "utf8", nbuffers=3)
+    thr = os.environ.get("STROM_LIKE_LONG_ROW", "256")
+    g = torch.Generator(device=dev)
+    g.manual_seed(7)
+
+    def table(lo, hi, nbytes):
+        rows = int(nbytes // ((lo + hi) / 2))
+        lens = torch.randint(lo, hi + 1, (rows,), device=dev, generator=g)
+        offs = torch.zeros(rows + 1, dtype=torch.int32, device=dev)
+        offs[1:] = torch.cumsum(lens, 0).to(torch.int32)
+        nch = int(offs[-1].item())
+        chars = torch.randint(97, 123, ((nch + 7) // 8 * 8,), dtype=torch.uint8, device=dev,
+                              generator=g)
+        qtab = torch.tensor([[offs.data_ptr(), 0, rows, 0, 0, chars.data_ptr(), nch]],
+                            dtype=torch.int64, device=dev)
+        return rows, nch, offs, chars, qtab
+
+    def rows_of(tag, tab, preds):
+        rows, nch, offs, chars, qtab = tab
+        nw = (rows + 63) // 64
+        bm = torch.empty(nw, dtype=torch.int64, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        for name, p in preds:
+            c = CP.compile_pred(p, col)
+            cnt.zero_()
+            CP.qual_batched(c, qtab, nw, bm, cnt)
+            sel = int(cnt.item())
+            log(f"{name}_{tag}", timed(lambda: CP.qual_batched(c, qtab, nw, bm, cnt)),
+                nch + 4 * (rows + 1))
+            print(f"  {name}_{tag}: {rows} rows, {nch} bytes, {sel} selected", file=sys.stderr)
+
+    P = CP.P
+    short = table(3, 24, min(n, 1 << 30) // 2)
+    rows_of("words", short, [
+        ("column_qual_str_eq", P("name") == "abc"),
+        ("column_qual_str_prefix", P("name").startswith("ab")),
+        ("column_qual_like_contains", P("name").contains("abc")),
+        ("column_qual_like_suffix", P("name").endswith("ab")),
+        ("column_qual_like", P("name").like("a%b_c%")),
+        ("column_qual_like_head", P("name").like("ab%")),
+    ])
+    del short
+    long_ = table(200, 2000, min(n, 1 << 30) // 2)
+    rows_of(f"long_t{thr}", long_, [
+        ("column_qual_str_prefix", P("name").startswith("ab")),
+        ("column_qual_like_contains", P("name").contains("abcd")),
+        ("column_qual_like_suffix", P("name").endswith("ab")),
+        ("column_qual_like", P("name").like("a%b_c%xyz%")),
+    ])
 
 
 def _agg_rows(n, dev, log, column_filter):

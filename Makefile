@@ -185,6 +185,15 @@ build/collike_fuzz: csrc/tests/collike_fuzz.cc csrc/kernels/collike.hip csrc/inc
 	  -Xarch_host -fno-sanitize-recover=all -fno-omit-frame-pointer \
 	  -o $@ csrc/tests/collike_fuzz.cc csrc/kernels/collike.hip
 
+# the select-list walk's host copy (batch lookup, row masking, every column
+# kind, the string span rule), host-only with ASan + UBSan
+build/colproject_fuzz: csrc/tests/colproject_fuzz.cc csrc/kernels/colproject.hip csrc/include/strom/strom.h
+	@mkdir -p build
+	$(HIPCC) -std=c++17 -O1 -g -Icsrc/include --offload-arch=$(ARCH) \
+	  -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
+	  -Xarch_host -fno-sanitize-recover=all -fno-omit-frame-pointer \
+	  -o $@ csrc/tests/colproject_fuzz.cc csrc/kernels/colproject.hip
+
 selftest: build/selftest build/selftest-asan build/selftest-tsan
 	STROM_STAT_SHM=0 ./build/selftest && STROM_STAT_SHM=0 ./build/selftest-asan && STROM_STAT_SHM=0 TSAN_OPTIONS=report_signal_unsafe=0 ./build/selftest-tsan
 

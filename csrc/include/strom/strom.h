@@ -674,6 +674,46 @@ int strom_bitmap_to_rows_str(const uint64_t *d_bitmap, uint64_t nwords,
                              int64_t *d_poff, uint8_t *d_pchars, uint8_t *d_pvalid,
                              uint64_t *d_char_cursor, void *stream);
 
+/* A select list (csrc/kernels/colproject.hip; Arrow scans:
+ * scan_where(quals, project=[...])): strom_bitmap_to_rows_proj / _str for up
+ * to STROM_PROJ_MAX_COLS columns in one walk of the bitmap.  The row ids are
+ * appended at *d_total, which advances by the rows appended, and every
+ * column's values are written at the same positions: FIXED `width` bytes per
+ * row, BOOL (Arrow LSB-first value bits) a 0/1 byte, STR32 / STR64 (offsets
+ * of 4 / 8 bytes in values, the characters in aux) the row's characters
+ * appended at the column's own device cursor *char_cursor in out_chars and
+ * their start written to out as an int64.  out_valid, when given, gets
+ * valid ? bit : 1 per selected row.  A malformed offset pair (negative,
+ * decreasing, past aux_len) gives an empty string and no read outside aux.
+ * Every column's table has the batches' nrows / word_base; a bit at or past
+ * its batch's rows is ignored.  Nothing is written at or past the final
+ * cursor positions.  `cols` is host memory, read before the call returns.
+ * -22: a bad argument (ncols 0 or > STROM_PROJ_MAX_COLS, a kind or width
+ * not listed, a misaligned output, two string columns on one cursor);
+ * -75: more than 2^32 blocks of 256 words; -12: no scratch; 0 and nothing
+ * done for nwords == 0. */
+#define STROM_PROJ_MAX_COLS 16
+enum { STROM_PROJ_FIXED = 1, STROM_PROJ_BOOL, STROM_PROJ_STR32, STROM_PROJ_STR64 };
+struct strom_proj_col {
+	int32_t  kind;
+	uint32_t width;        /* FIXED: 1, 2, 4, 8 or 16 bytes */
+	uint64_t table;        /* device: nbatches x strom_qual_batch of this column */
+	uint64_t out;          /* FIXED/BOOL: width (BOOL: 1) bytes per selected row; STR: int64 start per row */
+	uint64_t out_valid;    /* 0, or uint8 0/1 per selected row */
+	uint64_t out_chars;    /* STR: the characters */
+	uint64_t char_cursor;  /* STR: device uint64, advanced by the characters appended */
+};
+int strom_bitmap_to_rows_multi(const uint64_t *d_bitmap, uint64_t nwords,
+                               const struct strom_filter_batch *d_batches, uint32_t nbatches,
+                               int64_t *d_out, uint64_t *d_total,
+                               const struct strom_proj_col *cols, uint32_t ncols, void *stream);
+/* The same walk on the CPU, every pointer host memory (buffers of any
+ * alignment): the kernel's reference and the fuzzer's target. */
+int strom_bitmap_to_rows_multi_host(const uint64_t *bitmap, uint64_t nwords,
+                                    const struct strom_filter_batch *batches, uint32_t nbatches,
+                                    int64_t *out, uint64_t *total,
+                                    const struct strom_proj_col *cols, uint32_t ncols);
+
 /* Aggregates over the selection bitmap (csrc/kernels/colagg.hip; Arrow
  * scans: ArrowScan.aggregate): COUNT / SUM / MIN / MAX of one column's
  * selected valid rows, per key slot when a key column is given.

@@ -341,6 +341,12 @@ _SIGS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
+    "strom_bitmap_to_rows_multi": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                             C.c_void_p]),
+    "strom_bitmap_to_rows_multi_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_uint32]),
     "strom_column_agg_init": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "strom_column_agg_grid": (C.c_uint32, [C.c_uint64, C.c_uint32, C.c_uint32]),
     "strom_column_agg": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,

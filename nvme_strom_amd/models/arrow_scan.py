@@ -43,6 +43,7 @@ from .. import api
 from ..ops import colagg as A
 from ..ops import colgroup as G
 from ..ops import coljoin as J
+from ..ops import colproject as PJ
 from ..ops import coltopk as T
 from ..ops import decompress as D
 from ..ops.colexpr import E, ExprName, Program, compile_expr, expr_batched, host_expr, name_of
@@ -426,6 +427,151 @@ def _split_names(meta, names: List[str]) -> Tuple[List[str], List[str]]:
 
 
 @dataclass
+class ProjOut:
+    """One column of a select list (``scan_where(quals, project=[...])``):
+    the fields of a single projection's ScanOut, per column.  Device tensors
+    from ArrowScan.scan_where, numpy arrays of the same layout from the host
+    twin."""
+    name: str
+    values: object                # one value per selected row (utf8/binary: the characters)
+    valid: object = None          # uint8 0/1 per selected row when the column may hold nulls
+    column: Optional[Column] = None   # the column's type; None: an attribute of a JoinTable
+    dictionary: object = None     # decoded dictionary / the attribute's value per code
+    offsets: object = None        # utf8/binary: int64[selected + 1] into ``values``
+
+
+def _select_items(project) -> list:
+    """The items of a list ``project=`` checked among themselves: column
+    names (expressions as ExprName) and JoinAttrs, in the order given."""
+    items = list(project)
+    if not items:
+        raise ValueError("project=[]: an empty select list (project=None selects the row ids)")
+    if len(items) > PJ.MAX_COLS:
+        raise NotImplementedError(f"a select list of {len(items)} columns: at most "
+                                  f"{PJ.MAX_COLS} are gathered in one emit pass")
+    out = []
+    for it in items:
+        if isinstance(it, JoinAttr):
+            out.append(it)
+        elif isinstance(it, (str, E)):
+            out.append(name_of(it))
+        else:
+            raise TypeError(f"project=[...]: {it!r} is no column name, expression or dim[attr]")
+    keys = [("attr", id(c.table), c.name) if isinstance(c, JoinAttr) else ("col", str(c))
+            for c in out]
+    for k in keys:
+        if keys.count(k) > 1:
+            raise ValueError(f"project=[...]: {k[-1]!r} appears twice")
+    tabs = [id(c.table) for c in out if isinstance(c, JoinAttr)]
+    if len(set(tabs)) < len(tabs):
+        raise NotImplementedError("project=[...]: one attribute per JoinTable (the probe writes "
+                                  "one attribute's codes per leg)")
+    return out
+
+
+def _select_meta(xm, items: list) -> List[Optional[Column]]:
+    """The Column of each item of a select list (None: a JoinAttr), every
+    kind checked before anything is read: what a single projection takes,
+    and bool columns."""
+    schema = {c.name: c for c in xm.schema}
+    metas = []
+    for it in items:
+        if isinstance(it, JoinAttr):
+            metas.append(None)
+            continue
+        if it not in schema:
+            raise ValueError(f"no column {str(it)!r}")
+        c = schema[it]
+        strings = c.kind in ("utf8", "binary") and c.dictionary is None
+        if not c.supported or not (strings or c.storage in _TORCH or c.storage in ("d16", "b1")):
+            raise NotImplementedError(f"projection of {it} ({c.kind}): fixed-width, bool, "
+                                      "utf8/binary or dictionary-encoded columns")
+        metas.append(c)
+    return metas
+
+
+def _arrow_type(c: Column):
+    import pyarrow as pa
+    if c.kind in ("utf8", "binary"):
+        return {("utf8", False): pa.utf8(), ("utf8", True): pa.large_utf8(),
+                ("binary", False): pa.binary(), ("binary", True): pa.large_binary()}[
+                    (c.kind, bool(c.large))]
+    if c.kind == "bool":
+        return pa.bool_()
+    if c.kind == "decimal":
+        return pa.decimal128(c.precision, c.scale)
+    if c.kind == "date":
+        return pa.date32() if c.unit == "d" else pa.date64()
+    if c.kind == "time":
+        return pa.time32(c.unit) if c.bit_width == 32 else pa.time64(c.unit)
+    if c.kind == "timestamp":
+        return pa.timestamp(c.unit, tz=c.tz or None)
+    if c.kind == "duration":
+        return pa.duration(c.unit)
+    return pa.from_numpy_dtype(np.dtype(Column(c.name, c.kind, c.bit_width, c.signed).storage))
+
+
+def _arrow_array(c: Column, values: np.ndarray, valid, offsets=None):
+    """The pyarrow array of a column's gathered buffers (numpy, the layout of
+    ProjOut; ``c`` without its dictionary describes the values)."""
+    import pyarrow as pa
+    typ = _arrow_type(c)
+    if offsets is not None:
+        n = len(offsets) - 1
+        ot = np.int64 if c.large else np.int32
+        bufs = [pa.py_buffer(np.ascontiguousarray(offsets, dtype=ot)),
+                pa.py_buffer(np.ascontiguousarray(values, dtype=np.uint8))]
+    elif c.kind == "bool":
+        n = len(values)
+        bufs = [pa.py_buffer(np.packbits(np.asarray(values, np.uint8) != 0, bitorder="little"))]
+    else:
+        n = len(values)
+        bufs = [pa.py_buffer(np.ascontiguousarray(values))]
+    vbuf, nulls = None, 0
+    if valid is not None:
+        ok = np.asarray(valid) != 0
+        nulls = int(len(ok) - ok.sum())
+        if nulls:
+            vbuf = pa.py_buffer(np.packbits(ok, bitorder="little"))
+    return pa.Array.from_buffers(typ, n, [vbuf] + bufs, null_count=nulls)
+
+
+def _arrow_table(cols: List[ProjOut]):
+    """A pyarrow.Table of a select list's columns (numpy buffers), the
+    column types restored from the Column metadata."""
+    import pyarrow as pa
+    arrays, fields = [], []
+    for p in cols:
+        c = p.column
+        if c is None:
+            # dim[attr]: a dictionary array over the attribute's values
+            arr = pa.DictionaryArray.from_arrays(pa.array(np.asarray(p.values, np.int32)),
+                                                 pa.array(list(p.dictionary)))
+            nullable = True
+        elif c.dictionary is not None:
+            dv, dok = p.dictionary
+            vc = replace(c, dictionary=None)
+            if isinstance(dv, tuple):
+                darr = _arrow_array(vc, dv[1], dok, offsets=dv[0])
+            else:
+                darr = _arrow_array(vc, np.asarray(dv), dok)
+            idx = _arrow_array(Column(c.name, "int", c.dictionary.index_bits,
+                                      c.dictionary.index_signed), p.values, p.valid)
+            arr = pa.DictionaryArray.from_arrays(idx, darr, ordered=c.dictionary.ordered)
+            nullable = c.nullable
+        else:
+            arr = _arrow_array(c, p.values, p.valid, p.offsets)
+            nullable = True if isinstance(c.name, ExprName) else c.nullable
+        arrays.append(arr)
+        fields.append(pa.field(str(p.name), arr.type, nullable=nullable))
+    return pa.Table.from_arrays(arrays, schema=pa.schema(fields))
+
+
+def _to_host(x):
+    return x.cpu().numpy() if isinstance(x, torch.Tensor) else x
+
+
+@dataclass
 class ScanOut:
     rows: int
     selected: int
@@ -441,6 +587,47 @@ class ScanOut:
     offsets: Optional[torch.Tensor] = None  # utf8/binary projection: int64[selected + 1]
                                             # into ``values`` (the characters, uint8)
     exprs: list = field(default_factory=list)   # the computed columns' Programs
+    # project=[...]: one ProjOut per item, in the order given (values / valid /
+    # column / dictionary / offsets above are then None)
+    columns: Optional[List[ProjOut]] = None
+
+    def to_arrow(self):
+        """The selected rows as a pyarrow.Table: the select list's columns
+        (or the one projected column), one device -> host copy per buffer,
+        the types restored from the file's schema: temporal units and time
+        zone, decimal128(p, s) from the (lo, hi) words, dictionary columns as
+        DictionaryArrays, utf8 / large_utf8 / binary from offsets and
+        characters, ``dim[attr]`` as a dictionary array over the attribute's
+        values, expressions as int64 / float64."""
+        cols = self.columns
+        if cols is None:
+            if self.values is None:
+                raise ValueError("to_arrow: the scan projected no column")
+            name = self.column.name if self.column is not None else "attr"
+            cols = [ProjOut(name, self.values, self.valid, self.column, self.dictionary,
+                            self.offsets)]
+        return _arrow_table([ProjOut(p.name, _to_host(p.values), _to_host(p.valid), p.column,
+                                     p.dictionary, _to_host(p.offsets)) for p in cols])
+
+
+@dataclass
+class _SelItem:
+    """One column of a select list as _compute and _emit see it."""
+    kind: int                     # ops/colproject FIXED / BOOL / STR32 / STR64
+    width: int
+    pcol: Optional[int] = None    # plan column; None: a join attribute's codes, in
+    buf: int = -1                 # ... the slot's key buffer (-1) or leg buffer ``buf``
+    out: Optional[torch.Tensor] = None
+    valid: Optional[torch.Tensor] = None
+    chars: Optional[torch.Tensor] = None
+    cursor: Optional[torch.Tensor] = None     # view of one word of the scan's cursors
+
+
+@dataclass
+class _SelRun:
+    """A scan's select list: its columns and their kernel descriptors."""
+    items: List[_SelItem]
+    cols: np.ndarray              # ops/colproject.proj_cols, tables filled in per group
 
 
 @dataclass
@@ -520,6 +707,7 @@ class _Run:
     owidth: int = 4                              # offset bytes of a projected utf8/binary column
     pattr: bool = False                          # project the joined attribute's codes
     pcol: Optional[int] = None                   # plan column of the projection
+    sel: Optional[_SelRun] = None                # project=[...]: the select list instead
     # aggregate
     agg: Optional[_AggSpec] = None
     block: Optional[torch.Tensor] = None         # the scan's accumulator block
@@ -1196,6 +1384,8 @@ class ArrowScan:
                 d_proj = d_codes                 # the joined attribute's codes
             elif run.pcol is not None:
                 d_proj = t.qual(run.pcol) if run.pchars is not None else t.dev5(run.pcol)
+            elif run.sel is not None:
+                d_proj = self._select_tables(s, g, t, run.sel)
             s.keep += [d_rows] + ([d_proj] if d_proj is not None else [])
         self._emit(s, g, run, d_rows, d_proj, args, slabs)
         run.bytes_read += g.read_bytes
@@ -1400,6 +1590,21 @@ class ArrowScan:
                                 stream=s.stream)
         return s.bitmap, d_h[-1]
 
+    def _select_tables(self, s: _Slot, g: _Group, t: _Tables, sel: _SelRun) -> torch.Tensor:
+        """project=[...]: the strom_qual_batch table of every column of the
+        select list — a stored or computed column's own, a join attribute's
+        that of the buffer the probe left its codes in — stacked into one
+        upload (columns, batches, 7)."""
+        tabs = []
+        for it in sel.items:
+            if it.pcol is None:
+                t7 = g.table.copy()
+                t7[:, :BATCH_FIELDS] = self._code_table(s, g, it.buf)
+                tabs.append(t7)
+            else:
+                tabs.append(t._host(it.pcol))
+        return self._upload(s, PJ.stack_tables(tabs))
+
     def _select(self, s: _Slot, g: _Group, t: _Tables, tr: _TopRun, bitmap: torch.Tensor,
                 d_codes: Optional[torch.Tensor]) -> tuple:
         """ORDER BY ... LIMIT k: the group's candidates over the selection the
@@ -1472,7 +1677,11 @@ class ArrowScan:
                 # the group's candidates into the scan's k best, in group order;
                 # the new threshold is there for the launches not yet queued
                 T.merge(run.top.state, slabs[0], slabs[1], stream=es)
-            if run.pchars is not None:
+            if run.sel is not None:
+                # the select list: ids and every column in one walk
+                PJ.bitmap_to_rows_multi(s.bitmap, g.words, d_rows, run.out, run.cursor,
+                                        run.sel.cols, d_proj, stream=es)
+            elif run.pchars is not None:
                 bitmap_to_rows_str(s.bitmap, g.words, d_rows, run.out, run.cursor, d_proj,
                                    run.owidth, run.poff, run.pchars, run.ccursor,
                                    pvalid=run.pvalid, stream=es)
@@ -1615,7 +1824,15 @@ class ArrowScan:
         A predicate may be on an expression (ops/colexpr.E: ``E("a") + E("b") <
         5``, every numeric operator) and ``project`` may be one (its int64 or
         float64 values): computed on the device per group (colexpr.hip), at
-        most four distinct expressions per scan."""
+        most four distinct expressions per scan.
+        ``project=[...]`` — a list or tuple, also of one — is a select list:
+        up to 16 such items, and bool columns (gathered as uint8 0/1), all
+        gathered in one emit pass (csrc/kernels/colproject.hip) and returned
+        as ``ScanOut.columns``, one ProjOut per item in the order given;
+        ``ScanOut.to_arrow()`` assembles them.  No item twice, one attribute
+        per JoinTable."""
+        if isinstance(project, (list, tuple)):
+            return self._scan_select(quals, project, batches, join)
         pattr = project if isinstance(project, JoinAttr) else None
         join = _check_join(self.meta, join, pattr)
         if pattr is not None:
@@ -1689,6 +1906,93 @@ class ArrowScan:
                        valid=pvalid[:count] if pvalid is not None else None,
                        column=pmeta, dictionary=pdict, offsets=offsets,
                        exprs=[x.prog for x in run.exprs])
+
+    def _scan_select(self, quals, project, batches, join) -> ScanOut:
+        """scan_where with a select list: the stages of the single form up to
+        the emit, which writes the row ids and every column of the list in
+        one walk of each group's bitmap (ops/colproject.py), on the emit
+        stream, in group order, behind the shared cursors."""
+        items = _select_items(project)
+        attrs = [it for it in items if isinstance(it, JoinAttr)]
+        join = _check_join(self.meta, join, attrs)
+        cl = _named_clauses(quals) if (quals or join is None) else []
+        t0 = time.perf_counter()
+        pnames = [it for it in items if not isinstance(it, JoinAttr)]
+        names = _scanned(cl, join, pnames)
+        xm = _with_exprs(self.meta, names)
+        metas = _select_meta(xm, items)
+        names, full = _split_names(xm, names)
+        cols, nrows, groups = self._resolve(names, batches)
+        spec = [[(full.index(p.col), self._compile(p, xm)) for p in c] for c in cl]
+        t_plan = time.perf_counter()
+        cap = max(nrows, 1)
+        new = lambda *shape, dtype: torch.empty(*shape, dtype=dtype, device=self.device)
+        out = new(cap, dtype=torch.int64)
+        # the row cursor, then one character cursor per string column
+        nstr = sum(m is not None and m.kind in ("utf8", "binary") and m.dictionary is None
+                   for m in metas)
+        cursors = torch.zeros(1 + nstr, dtype=torch.int64, device=self.device)
+        sel, outs, k = [], [], 0
+        star = isinstance(join, StarJoin)
+        for it, m in zip(items, metas):
+            if m is None:
+                # the joined attribute's codes: int32 per row in the probe's buffer
+                si = _SelItem(PJ.FIXED, 4, None, attrs.index(it) if star else -1,
+                              out=new(cap, dtype=torch.int32))
+                outs.append(ProjOut(it.name, None, None, None, it.values))
+                sel.append(si)
+                continue
+            pcol = full.index(it)
+            st = m.storage
+            if m.kind in ("utf8", "binary") and m.dictionary is None:
+                k += 1
+                nch = sum(int(g.aux_len[:, pcol].sum()) for g in groups)
+                si = _SelItem(PJ.STR64 if m.large else PJ.STR32, 0, pcol,
+                              out=new(cap + 1, dtype=torch.int64),
+                              chars=new(max(nch, 1), dtype=torch.uint8), cursor=cursors[k:k + 1])
+            elif st == "b1":
+                si = _SelItem(PJ.BOOL, 0, pcol, out=new(cap, dtype=torch.uint8))
+            elif st == "d16":
+                si = _SelItem(PJ.FIXED, 16, pcol, out=new((cap, 2), dtype=torch.int64))
+            else:
+                si = _SelItem(PJ.FIXED, np.dtype(st).itemsize, pcol, out=new(cap, dtype=_TORCH[st]))
+            if m.nullable if pcol >= len(names) else any(bool(g.has_valid[pcol]) for g in groups):
+                si.valid = new(cap, dtype=torch.uint8)
+            sel.append(si)
+            outs.append(ProjOut(str(it), None, None, m,
+                                self.dictionary(it) if m.dictionary is not None else None))
+        if not groups or nrows == 0:
+            for si, po in zip(sel, outs):
+                po.values = si.out[:0] if si.chars is None else si.chars[:0]
+                po.offsets = self._zero() if si.chars is not None else None
+            return ScanOut(nrows, 0, out[:0], {"total_s": time.perf_counter() - t0}, columns=outs)
+        ptr = lambda x: x.data_ptr() if x is not None else 0
+        desc = PJ.proj_cols([(si.kind, si.width, ptr(si.out), ptr(si.valid), ptr(si.chars),
+                              ptr(si.cursor)) for si in sel])
+        run = _Run(self._zero(), self._zero(), out=out, cursor=cursors[0:1],
+                   exprs=self._expr_runs(xm, full, cl), sel=_SelRun(sel, desc))
+        if join is not None:
+            run.join = self._join_run(join, names, attrs)
+        t_alloc = self._drive(groups, spec, run)
+        got = torch.cat([run.count, run.err, cursors]).tolist()
+        count, err, cursor, nchars = got[0], got[1], got[2], got[3:]
+        secs = self._seconds(run, t0, t_plan, t_alloc)
+        self._check_decoded(err, names)
+        if cursor != count:
+            raise RuntimeError(f"row emit mismatch: {cursor} ids for {count} selected")
+        k = 0
+        for si, po in zip(sel, outs):
+            po.valid = si.valid[:count] if si.valid is not None else None
+            if si.chars is not None:
+                si.out[count] = nchars[k]
+                po.values, po.offsets = si.chars[:nchars[k]], si.out[:count + 1]
+                k += 1
+            else:
+                po.values = si.out[:count]
+        secs["timeline_ms"] = [(k, e, round((t - t_alloc) * 1e3, 3)) for k, e, t in run.marks]
+        return ScanOut(nrows, int(count), out[:count], secs, bytes_read=run.bytes_read,
+                       column_bytes=run.column_bytes, groups=len(groups),
+                       exprs=[x.prog for x in run.exprs], columns=outs)
 
     def aggregate(self, quals, aggs, by=None, batches: Optional[Tuple[int, int]] = None,
                   join: Union[Join, StarJoin, None] = None) -> "AggOut":
@@ -1939,6 +2243,81 @@ class HostScanOut:
     valid: Optional[np.ndarray] = None
     dictionary: object = None          # project=dim[attr]: the value of each code
     exprs: list = field(default_factory=list)   # the computed columns' Programs
+    # project=[...]: one ProjOut of numpy arrays per item, laid out as the
+    # device scan's (values / valid / dictionary above are then None)
+    columns: Optional[List[ProjOut]] = None
+
+    def to_arrow(self):
+        """The select list's columns as a pyarrow.Table (ScanOut.to_arrow)."""
+        if self.columns is None:
+            raise ValueError("to_arrow: host_scan_where(project=[...]) assembles a table")
+        return _arrow_table(self.columns)
+
+
+def _host_select(path: str, quals, project, batches, meta: ArrowFile, dicts: dict,
+                 join) -> HostScanOut:
+    """host_scan_where with a select list: every column gathered per record
+    batch with the rows the qualifiers and the join select, in the layout of
+    the device scan's ProjOut."""
+    items = _select_items(project)
+    attrs = [it for it in items if isinstance(it, JoinAttr)]
+    join = _check_join(meta, join, attrs)
+    cl = _named_clauses(quals) if (quals or join is None) else []
+    pnames = [it for it in items if not isinstance(it, JoinAttr)]
+    meta = _with_exprs(meta, [p.col for c in cl for p in c] + pnames)
+    metas = _select_meta(meta, items)
+    base = np.concatenate([[0], np.cumsum(meta.rows)]).astype(np.int64)
+    nrows = 0
+    ids: List[np.ndarray] = []
+    parts: List[list] = [[] for _ in items]
+    for bi, b, data, m, jrow in _host_batches(path, meta, dicts, cl, join, pnames, batches):
+        nrows += b.length
+        sel = np.flatnonzero(m)
+        ids.append(sel + base[bi])
+        for k, (it, c) in enumerate(zip(items, metas)):
+            if c is None:
+                codes = it.codes[jrow[_leg_of(join, it)][sel]] if len(it.codes) else \
+                    np.zeros(0, np.int32)
+                parts[k].append((codes.astype(np.int32), None, None))
+                continue
+            v, ok = data[it]
+            okb = ok[sel].astype(np.uint8) if ok is not None else np.ones(len(sel), np.uint8)
+            if isinstance(v, tuple):
+                offs, chars = v
+                a = offs[sel]
+                ln = offs[sel + 1] - a if len(sel) else a
+                st = np.cumsum(ln) - ln
+                idx = np.repeat(a - st, ln) + np.arange(int(ln.sum()))
+                parts[k].append((ln, okb, np.asarray(chars)[idx]))
+            elif c.kind == "decimal" and c.dictionary is None:
+                raw = b"".join(int(x).to_bytes(16, "little", signed=True) for x in v[sel])
+                parts[k].append((np.frombuffer(raw, "<i8").reshape(-1, 2), okb, None))
+            else:
+                x = np.asarray(v)[sel]
+                parts[k].append((x.astype(np.uint8) if c.kind == "bool" and c.dictionary is None
+                                 else x, okb, None))
+    cols = []
+    for it, c, p in zip(items, metas, parts):
+        if c is None:
+            cols.append(ProjOut(it.name, np.concatenate([x[0] for x in p]) if p else
+                                np.zeros(0, np.int32), None, None, it.values))
+            continue
+        ok = np.concatenate([x[1] for x in p]) if p else np.zeros(0, np.uint8)
+        po = ProjOut(str(it), None, None if ok.all() else ok, c,
+                     _dictionary(meta, path, dicts, it) if c.dictionary is not None else None)
+        if c.kind in ("utf8", "binary") and c.dictionary is None:
+            ln = np.concatenate([x[0] for x in p]) if p else np.zeros(0, np.int64)
+            po.values = np.concatenate([x[2] for x in p]) if p else np.zeros(0, np.uint8)
+            po.offsets = np.concatenate([[0], np.cumsum(ln)]).astype(np.int64)
+        elif p:
+            po.values = np.concatenate([x[0] for x in p])
+        else:
+            st = c.storage
+            po.values = np.zeros((0, 2), np.int64) if st == "d16" else \
+                np.zeros(0, np.uint8 if st == "b1" else st)
+        cols.append(po)
+    return HostScanOut(nrows, np.concatenate(ids) if ids else np.zeros(0, np.int64),
+                       exprs=list(getattr(meta, "progs", {}).values()), columns=cols)
 
 
 def _order_name(order_by):
@@ -2067,6 +2446,8 @@ def host_scan_where(path: str, quals, project=None,
     reference point for the GPU path and a scan for machines without one."""
     meta = meta if meta is not None else read_metadata(path)
     dicts = dicts if dicts is not None else {}
+    if isinstance(project, (list, tuple)):
+        return _host_select(path, quals, project, batches, meta, dicts, join)
     pattr = project if isinstance(project, JoinAttr) else None
     join = _check_join(meta, join, pattr)
     if pattr is not None:
@@ -2074,7 +2455,7 @@ def host_scan_where(path: str, quals, project=None,
     project = name_of(project)
     cl = _named_clauses(quals) if (quals or join is None) else []
     meta = _with_exprs(meta, [p.col for c in cl for p in c] + ([project] if project else []))
-    base = np.concatenate([[0], np.cumsum(meta.rows)]).astype(np.int64)
+    base =np.concatenate([[0], np.cumsum(meta.rows)]).astype(np.int64)
     nrows = 0
     ids, vals, valid = [], [], []
     pleg = _leg_of(join, pattr) if pattr is not None else None

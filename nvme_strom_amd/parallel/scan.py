@@ -137,6 +137,10 @@ class DistributedArrowScan:
                    project: Optional[str] = None, gather: str = "all") -> DistScanOut:
         if gather not in ("all", "none"):
             raise ValueError(f"gather {gather!r}")
+        if isinstance(project, (list, tuple)):
+            raise NotImplementedError("a select list (project=[...]) is not gathered across "
+                                      "ranks: ArrowScan.scan_where takes one on a single GPU; "
+                                      "here project names one column")
         t0 = time.perf_counter()
         # every spelling of a qualifier list (tuples, P(...) predicates, Or)
         from ..ops.colpred import clauses

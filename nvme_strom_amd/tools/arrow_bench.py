@@ -637,6 +637,76 @@ def expr_row(path: str, fd: int, a, col) -> dict:
     return row
 
 
+def select_row(path: str, fd: int, a, col) -> dict:
+    """``SELECT id, x, val WHERE val BETWEEN .. AND x BETWEEN ..`` as one
+    select-list scan (``project=["id", "x", "val"]``: one emit pass,
+    colproject.hip) alternated with the same three columns fetched by three
+    single-column scans of the same file.  The file is evicted before every
+    scan; every column of both forms is verified against numpy."""
+    import torch
+
+    import nvme_strom_amd as S
+    from nvme_strom_amd.models.arrow_scan import ArrowScan
+    quals = [("val", 100_000, 599_999), ("x", 0.25, 0.75)]
+    names = ["id", "x", "val"]
+    sc = ArrowScan(path, "cuda", slot_bytes=a.slot_mib << 20, nslots=a.nslots or None,
+                   chunk_sz=(a.chunk_kib << 10) or None)
+
+    def timed(fn):
+        S.evict_file(fd)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = fn()
+        return time.perf_counter() - t, out
+
+    def three():
+        return [sc.scan_where(quals, project=n) for n in names]
+    list_s, three_s = [], []
+    try:
+        timed(lambda: sc.scan_where(quals, project=names))       # cold: plans, slots, code
+        timed(three)
+        for k in range(max(1, a.agg_pairs)):
+            for what in (("list", "three") if k % 2 == 0 else ("three", "list")):
+                if what == "list":
+                    dt, out = timed(lambda: sc.scan_where(quals, project=names))
+                    list_s.append(dt)
+                else:
+                    dt, singles = timed(three)
+                    three_s.append(dt)
+            _log(f"select pair {k}: list {list_s[-1] * 1e3:.1f} ms, three scans "
+                 f"{three_s[-1] * 1e3:.1f} ms")
+    finally:
+        sc.close()
+    m = None
+    for name, lo, hi in quals:
+        vals, valid = col(name)
+        mm = (vals >= lo) & (vals <= hi)
+        if valid is not None:
+            mm &= valid
+        m = mm if m is None else m & mm
+    ref = np.flatnonzero(m)
+    ok = bool(np.array_equal(out.indices.cpu().numpy(), ref))
+    for n, c, one in zip(names, out.columns, singles):
+        want = col(n)[0][ref]
+        ok = ok and bool(np.array_equal(c.values.cpu().numpy(), want)) and \
+            bool(np.array_equal(one.values.cpu().numpy(), want))
+    ratios = [x / y for x, y in zip(list_s, three_s)]
+    row = dict(project=names, quals=[repr(q) for q in quals], selected=out.selected,
+               rows_verified=int(len(ref)) if ok else 0, verified=ok,
+               bytes_read=out.bytes_read, column_bytes=out.column_bytes, groups=out.groups,
+               list_ms=[round(x * 1e3, 2) for x in list_s],
+               three_scans_ms=[round(x * 1e3, 2) for x in three_s],
+               list_median_ms=round(float(np.median(list_s)) * 1e3, 2),
+               three_scans_median_ms=round(float(np.median(three_s)) * 1e3, 2),
+               list_spread_ms=[round(min(list_s) * 1e3, 2), round(max(list_s) * 1e3, 2)],
+               three_scans_spread_ms=[round(min(three_s) * 1e3, 2), round(max(three_s) * 1e3, 2)],
+               median_ratio_list_over_three=round(float(np.median(ratios)), 4),
+               list_breakdown_s={k: round(v, 4) for k, v in out.seconds.items()
+                                 if isinstance(v, float)})
+    _log(json.dumps(row))
+    return row
+
+
 def topk_rows(path: str, fd: int, a, col) -> dict:
     """ORDER BY ... LIMIT k rows: ``top val k=100`` (the ``val`` row's range
     as qualifier, ORDER BY val LIMIT 100), the same under qual2's two-column
@@ -838,6 +908,9 @@ def main(argv=None) -> int:
     ap.add_argument("--expr", action="store_true",
                     help="add the computed-column row: aggregate sum(E(val) * E(x)) alternated "
                          "with aggregate sum(val), sum(x) (--agg-pairs pairs)")
+    ap.add_argument("--select", action="store_true",
+                    help="add the select-list row: scan_where(qual2, project=[id, x, val]) "
+                         "alternated with the three single-column scans (--agg-pairs pairs)")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     import torch
@@ -955,6 +1028,8 @@ def main(argv=None) -> int:
             res["topk"] = topk_rows(path, fd, a, col)
         if a.expr:
             res["expr"] = expr_row(path, fd, a, col)
+        if a.select:
+            res["select"] = select_row(path, fd, a, col)
     finally:
         os.close(fd)
     if a.hashagg:
@@ -1015,7 +1090,8 @@ def main(argv=None) -> int:
         all(r["verified"] for r in res.get("topk", {}).values()) and \
         res.get("hashagg", {}).get("verified", True) and \
         res.get("hashagg2", {}).get("verified", True) and \
-        res.get("expr", {}).get("verified", True)
+        res.get("expr", {}).get("verified", True) and \
+        res.get("select", {}).get("verified", True)
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:

@@ -42,7 +42,9 @@ def main(argv=None):
                          "topk (ORDER BY ... LIMIT k select + merge next to column_filter_i64), "
                          "expr (computed columns next to column_filter_i64), "
                          "like (column_qual_like: LIKE / contains / endswith next to the string "
-                         "equality and prefix qualifiers, short words and long rows)")
+                         "equality and prefix qualifiers, short words and long rows), "
+                         "rows_multi (bitmap_to_rows_multi: a select list in one emit pass next "
+                         "to the single-column emit kernels once per column)")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     only = set(a.only.split(","))
@@ -200,11 +202,113 @@ def main(argv=None):
         _expr_rows(n, dev, log, column_filter)
     if "like" in only:
         _like_rows(n, dev, log)
+    if "rows_multi" in only:
+        _rows_multi_rows(dev, log, res)
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:
             f.write(js)
     print(js)
+
+
+def _rows_multi_rows(dev, log, res, rows=1 << 25):
+    """bitmap_to_rows_multi (colproject.hip: a select list in one emit pass)
+    next to the single-column emit kernels of colfilter.hip
+    (bitmap_to_rows with a projection, bitmap_to_rows_str), called once per
+    column: 33.5M rows in one batch at 1 / 10 / 50 / 100 % selected, for one
+    and four 8-byte columns, eight columns of mixed widths and a utf8 column
+    of 3-24-byte words.  Every row is the median of three timings of five
+    calls, the two forms alternated (``spread_ms``: the three); GB/s counts, for both forms, the bytes
+    the select list must move: the bitmap, the row ids, and per column the
+    selected values read and written (strings: 8 B of offsets read and
+    written per row + the characters twice).  ``<set>_<pct>_ratio``: the
+    single-column kernels' time over the select list's."""
+    from nvme_strom_amd.ops import colproject as PJ
+    from nvme_strom_amd.ops.colfilter import bitmap_to_rows, bitmap_to_rows_str
+    g = torch.Generator(device=dev)
+    g.manual_seed(11)
+    nw = rows // 64
+    bt = torch.tensor([[0, 0, rows, 0, 0]], dtype=torch.int64, device=dev)
+    shifts = torch.arange(64, dtype=torch.int64, device=dev)
+    widths = {"1x8": [8], "4x8": [8] * 4, "8mixed": [1, 2, 4, 8, 16, 8, 4, 0]}   # 0: bool
+    srcs = {w: torch.randint(0, 256, (rows * max(w, 1) if w else rows // 8,), dtype=torch.uint8,
+                             device=dev, generator=g) for w in (1, 2, 4, 8, 16, 0)}
+    lens = torch.randint(3, 25, (rows,), device=dev, generator=g)
+    offs = torch.zeros(rows + 1, dtype=torch.int32, device=dev)
+    offs[1:] = torch.cumsum(lens, 0).to(torch.int32)
+    nch = int(offs[-1].item())
+    chars = torch.randint(97, 123, (nch,), dtype=torch.uint8, device=dev, generator=g)
+    del lens
+
+    def med2(a, b):
+        """The two forms alternated: (median, the three timings) of each."""
+        ta, tb = [], []
+        for _ in range(3):
+            ta.append(timed(a))
+            tb.append(timed(b))
+        return [(sorted(t)[1], [round(x * 1e3, 3) for x in t]) for t in (ta, tb)]
+
+    for pct in (1, 10, 50, 100):
+        if pct == 100:
+            bm = torch.full((nw,), -1, dtype=torch.int64, device=dev)
+        else:
+            bits = (torch.rand(rows, device=dev, generator=g) < pct / 100).view(nw, 64)
+            bm = (bits.to(torch.int64) << shifts).sum(1)
+            del bits
+        cap = rows                                  # every output sized for every row
+        out = torch.empty(cap, dtype=torch.int64, device=dev)
+        cur = torch.zeros(2, dtype=torch.int64, device=dev)
+        for tag, ws in list(widths.items()) + [("utf8", None)]:
+            if ws is None:
+                kinds = [(PJ.STR32, 0)]
+                tabs = torch.tensor([[[offs.data_ptr(), 0, rows, 0, 0, chars.data_ptr(), nch]]],
+                                    dtype=torch.int64, device=dev)
+                outs = [torch.empty(cap + 1, dtype=torch.int64, device=dev)]
+                och = torch.empty(nch, dtype=torch.uint8, device=dev)
+                per_row = 16 + 2 * nch / rows
+            else:
+                kinds = [(PJ.BOOL, 0) if w == 0 else (PJ.FIXED, w) for w in ws]
+                tabs = torch.tensor([[[srcs[w].data_ptr(), 0, rows, 0, 0, 0, 0]] for w in ws],
+                                    dtype=torch.int64, device=dev)
+                outs = [torch.empty(cap * max(w, 1), dtype=torch.uint8, device=dev) for w in ws]
+                och = None
+                per_row = sum(2 * w if w else 1.125 for w in ws)
+            cols = PJ.proj_cols([(k, w, o.data_ptr(), 0, och.data_ptr() if och is not None else 0,
+                                  cur[1:].data_ptr() if och is not None else 0)
+                                 for (k, w), o in zip(kinds, outs)])
+
+            def new():
+                cur.zero_()                         # the outputs hold one pass
+                PJ.bitmap_to_rows_multi(bm, nw, bt, out, cur[:1], cols, tabs)
+
+            # the single form's arguments: the 5-field tables and typed outputs
+            # (it has no bool projection: that column is left out of its side)
+            typed = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+            singles = [(tabs[i][:, :5].contiguous(),
+                        o.view(torch.int64).view(-1, 2) if w == 16 else o.view(typed[w]))
+                       for i, ((k, w), o) in enumerate(zip(kinds, outs)) if k == PJ.FIXED]
+
+            def old():
+                if och is not None:
+                    cur.zero_()
+                    bitmap_to_rows_str(bm, nw, bt, out, cur[:1], tabs[0], 4, outs[0], och, cur[1:])
+                for t5, o in singles:
+                    cur.zero_()
+                    bitmap_to_rows(bm, nw, bt, out, cur[:1], proj=t5, proj_out=o)
+            new()
+            torch.cuda.synchronize()
+            sel = int(cur[0].item())
+            nbytes = nw * 8 + sel * (8 + per_row)
+            (t_new, sp_new), (t_old, sp_old) = med2(new, old)
+            log(f"rows_multi_{tag}_{pct}", t_new, nbytes)
+            log(f"rows_proj_each_{tag}_{pct}", t_old, nbytes)
+            res[f"rows_multi_{tag}_{pct}"].update(spread_ms=sp_new, selected=sel)
+            res[f"rows_proj_each_{tag}_{pct}"].update(spread_ms=sp_old)
+            res[f"rows_multi_{tag}_{pct}_ratio"] = round(t_old / t_new, 3)
+            print(f"  {tag} {pct}%: {sel} rows, single-column kernels / select list = "
+                  f"{t_old / t_new:.2f}", file=sys.stderr, flush=True)
+            del outs, och, tabs
+        del bm, out
 
 
 def _like_rows(n, dev, log):

@@ -194,6 +194,15 @@ build/colproject_fuzz: csrc/tests/colproject_fuzz.cc csrc/kernels/colproject.hip
 	  -Xarch_host -fno-sanitize-recover=all -fno-omit-frame-pointer \
 	  -o $@ csrc/tests/colproject_fuzz.cc csrc/kernels/colproject.hip
 
+# the radix sort's host copy (encode, the three steps of a pass, the gather
+# and the character copy), host-only with ASan + UBSan
+build/colsort_fuzz: csrc/tests/colsort_fuzz.cc csrc/kernels/colsort.hip csrc/include/strom/strom.h
+	@mkdir -p build
+	$(HIPCC) -std=c++17 -O1 -g -Icsrc/include --offload-arch=$(ARCH) \
+	  -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
+	  -Xarch_host -fno-sanitize-recover=all -fno-omit-frame-pointer \
+	  -o $@ csrc/tests/colsort_fuzz.cc csrc/kernels/colsort.hip
+
 selftest: build/selftest build/selftest-asan build/selftest-tsan
 	STROM_STAT_SHM=0 ./build/selftest && STROM_STAT_SHM=0 ./build/selftest-asan && STROM_STAT_SHM=0 TSAN_OPTIONS=report_signal_unsafe=0 ./build/selftest-tsan
 

@@ -1044,6 +1044,98 @@ int strom_topk_host_select(int type, uint32_t flags, uint32_t k, const uint64_t 
                            uint32_t nbatches, const uint64_t *state, uint64_t *slabs);
 int strom_topk_host_merge(uint32_t k, const uint64_t *slabs, uint32_t nslabs, uint64_t *state);
 
+/* ORDER BY on several columns (csrc/kernels/colsort.hip; Arrow scans:
+ * scan_where(quals, project=[...], order_by=[...], limit=, offset=)): a stable
+ * LSD radix sort over the n selected rows a select list's emit left in HBM —
+ * per column its values and, when it may hold nulls, one validity byte (0/1)
+ * per row.  The order is strom_column_topk's: a value before a NaN before a
+ * null in both directions, -0.0 equal to +0.0, equal keys in the order they
+ * came in.
+ *
+ * All state is the caller's: two uint64 key arrays and two uint32 permutation
+ * arrays of n entries each (24 bytes per row) and a work table of
+ * strom_sort_work_bytes(n) bytes: 256 uint32 counts per tile of
+ * STROM_SORT_TILE keys, digit-major, and 256 digit totals behind them.
+ * n < 2^32.
+ *
+ * strom_sort_encode writes key[i] = the key of values[perm[i]]: the value at
+ * the storage type's own width (type: STROM_COL_I8 .. U64, F32, F64) — sign
+ * bit flipped for signed integers, the monotone float map with -0.0 folded
+ * into +0.0, every bit of the width inverted with STROM_SORT_DESC, 0 for a
+ * NaN or a null (valid, may be NULL: no nulls).  With STROM_SORT_CLASS the
+ * key is the class instead: 0 a value, 1 a NaN, 2 a null.  With
+ * STROM_SORT_FIRST perm is written (perm[i] = i), not read.  A permutation
+ * entry >= n gives key 0.  A column is sorted by one strom_sort_pass per byte
+ * of its storage type, shift = 0, 8, ..., and where it is a float type or has
+ * nulls by a CLASS encode and one more pass at shift 0; the columns go from
+ * the least significant to the most.
+ *
+ * strom_sort_pass: one stable 8-bit pass (key_in, perm_in) -> (key_out,
+ * perm_out) by the digit at `shift` (a multiple of 8 up to 56): a histogram
+ * launch (one workgroup per tile, its counts into its own column of the
+ * table, no global atomics), a scan launch (workgroup d turns row d into
+ * exclusive prefixes, STROM_SORT_SCAN_THREADS entries a trip, and stores the
+ * row's total) and a scatter launch.  No workgroup waits for another.
+ *
+ * strom_sort_apply: out[i] = in[perm[first + i]] for i < count (first and
+ * count are cut to n) for the row ids (d_rows_in / d_rows_out, both or
+ * neither) and up to STROM_SORT_MAX_COLS columns in one launch; `cols` is
+ * host memory.  STROM_SORT_FIXED: `width` bytes per row (1, 2, 4, 8 or 16);
+ * STROM_SORT_LEN: `in` the int64 starts of a string column (n + 1 of them),
+ * `out` receives the row's length as int64.  out_valid (0: none) receives
+ * in_valid's byte (in_valid 0: 1).  A permutation entry >= n writes zeros and
+ * adds one to *d_err; nothing is read out of bounds.
+ *
+ * strom_sort_chars copies a string column's characters in output order:
+ * d_out_off the count + 1 int64 output offsets (the exclusive prefix of
+ * strom_sort_apply's lengths), in_len the bytes of d_in_chars, out_cap those
+ * of d_out_chars (4-byte aligned for whole-dword stores).
+ *
+ * Every entry returns -22 and launches nothing for a null pointer, n >= 2^32,
+ * an unknown type, flag, kind or width, more than STROM_SORT_MAX_COLS
+ * columns; n = 0 (or an empty window) returns 0 without a launch.  The
+ * strom_sort_*_host functions are the same steps on the CPU over host
+ * pointers (csrc/tests/colsort_fuzz.cc runs them under ASan + UBSan). */
+#define STROM_SORT_TILE 4096
+#define STROM_SORT_SCAN_THREADS 256
+#define STROM_SORT_MAX_COLS 16
+#define STROM_SORT_DESC 1
+#define STROM_SORT_CLASS 2
+#define STROM_SORT_FIRST 4
+enum { STROM_SORT_FIXED = 1, STROM_SORT_LEN = 2 };
+struct strom_sort_col {
+  uint32_t kind;
+  uint32_t width;
+  uint64_t in;
+  uint64_t out;
+  uint64_t in_valid;
+  uint64_t out_valid;
+};
+uint64_t strom_sort_work_bytes(uint64_t n);
+int strom_sort_encode(int type, uint32_t flags, const void *d_values, const uint8_t *d_valid,
+                      uint32_t *d_perm, uint64_t n, uint64_t *d_key, void *stream);
+int strom_sort_pass(const uint64_t *d_key_in, const uint32_t *d_perm_in, uint64_t *d_key_out,
+                    uint32_t *d_perm_out, uint64_t n, uint32_t shift, uint32_t *d_work,
+                    void *stream);
+int strom_sort_apply(const uint32_t *d_perm, uint64_t n, uint64_t first, uint64_t count,
+                     const int64_t *d_rows_in, int64_t *d_rows_out,
+                     const struct strom_sort_col *cols, uint32_t ncols, uint64_t *d_err,
+                     void *stream);
+int strom_sort_chars(const uint32_t *d_perm, uint64_t n, uint64_t first, uint64_t count,
+                     const int64_t *d_in_off, const uint8_t *d_in_chars, uint64_t in_len,
+                     const int64_t *d_out_off, uint8_t *d_out_chars, uint64_t out_cap,
+                     void *stream);
+int strom_sort_encode_host(int type, uint32_t flags, const void *values, const uint8_t *valid,
+                           uint32_t *perm, uint64_t n, uint64_t *key);
+int strom_sort_pass_host(const uint64_t *key_in, const uint32_t *perm_in, uint64_t *key_out,
+                         uint32_t *perm_out, uint64_t n, uint32_t shift, uint32_t *work);
+int strom_sort_apply_host(const uint32_t *perm, uint64_t n, uint64_t first, uint64_t count,
+                          const int64_t *rows_in, int64_t *rows_out,
+                          const struct strom_sort_col *cols, uint32_t ncols, uint64_t *err);
+int strom_sort_chars_host(const uint32_t *perm, uint64_t n, uint64_t first, uint64_t count,
+                          const int64_t *in_off, const uint8_t *in_chars, uint64_t in_len,
+                          const int64_t *out_off, uint8_t *out_chars, uint64_t out_cap);
+
 /* Computed columns (csrc/kernels/colexpr.hip; Arrow scans: an E expression
  * where a column name is accepted; nvme_strom_amd/ops/colexpr.py compiles
  * them): one arithmetic expression over up to STROM_EXPR_MAX_COLS source

@@ -393,6 +393,26 @@ _SIGS = {
                                          C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                          C.c_void_p, C.c_void_p]),
     "strom_topk_host_merge": (C.c_int, [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "strom_sort_work_bytes": (C.c_uint64, [C.c_uint64]),
+    "strom_sort_encode": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_uint64, C.c_void_p, C.c_void_p]),
+    "strom_sort_pass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                  C.c_uint32, C.c_void_p, C.c_void_p]),
+    "strom_sort_apply": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "strom_sort_chars": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                   C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                   C.c_void_p]),
+    "strom_sort_encode_host": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_uint64, C.c_void_p]),
+    "strom_sort_pass_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                       C.c_uint32, C.c_void_p]),
+    "strom_sort_apply_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                        C.c_void_p]),
+    "strom_sort_chars_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
+                                        C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                        C.c_void_p, C.c_uint64]),
     "strom_expr_check": (C.c_int, [C.c_void_p]),
     "strom_column_expr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),

@@ -44,6 +44,7 @@ from ..ops import colagg as A
 from ..ops import colgroup as G
 from ..ops import coljoin as J
 from ..ops import colproject as PJ
+from ..ops import colsort as SO
 from ..ops import coltopk as T
 from ..ops import decompress as D
 from ..ops.colexpr import E, ExprName, Program, compile_expr, expr_batched, host_expr, name_of
@@ -590,6 +591,11 @@ class ScanOut:
     # project=[...]: one ProjOut per item, in the order given (values / valid /
     # column / dictionary / offsets above are then None)
     columns: Optional[List[ProjOut]] = None
+    # order_by=: the normalized [(name, descending)] (None: file order), and
+    # the gather's error word (device, uint64 as int64: permutation entries
+    # that named no row; 0 unless the sort is broken), read by to_arrow
+    order: Optional[List[Tuple[str, bool]]] = None
+    sort_errors: Optional[torch.Tensor] = None
 
     def to_arrow(self):
         """The selected rows as a pyarrow.Table: the select list's columns
@@ -600,6 +606,9 @@ class ScanOut:
         characters, ``dim[attr]`` as a dictionary array over the attribute's
         values, expressions as int64 / float64."""
         cols = self.columns
+        if self.sort_errors is not None and int(self.sort_errors.item()):
+            raise RuntimeError(f"sort: {int(self.sort_errors.item())} permutation entries named "
+                               "no row")
         if cols is None:
             if self.values is None:
                 raise ValueError("to_arrow: the scan projected no column")
@@ -1796,7 +1805,8 @@ class ArrowScan:
                 "total_s": time.perf_counter() - t0}
 
     def scan_where(self, quals, project=None, batches: Optional[Tuple[int, int]] = None,
-                   join: Union[Join, StarJoin, None] = None) -> ScanOut:
+                   join: Union[Join, StarJoin, None] = None, order_by=None,
+                   limit: Optional[int] = None, offset: int = 0) -> ScanOut:
         """Row ids (int64, file order) of the rows every qualifier selects —
         a PG-Strom qualifier list.  ``quals`` items: ``(name, lo, hi)``
         ranges, ``(name, op, value)`` / ``P(name) <op> value`` predicates,
@@ -1830,9 +1840,34 @@ class ArrowScan:
         gathered in one emit pass (csrc/kernels/colproject.hip) and returned
         as ``ScanOut.columns``, one ProjOut per item in the order given;
         ``ScanOut.to_arrow()`` assembles them.  No item twice, one attribute
-        per JoinTable."""
+        per JoinTable.
+        ``order_by`` (with a select list) returns the rows sorted instead of
+        in file order: one item or a list of up to four, an item a column
+        name or an expression, alone (ascending) or in a pair with
+        "ascending" / "descending" — ``pyarrow.compute.sort_indices``'
+        sort keys, and its order with the default null placement: per column
+        a value before a NaN before a null in both directions, -0.0 equal to
+        +0.0, rows equal in every column in file order.  The kinds ``top``
+        orders: non-dictionary int8-64, uint8-64, float32/64, date, time,
+        timestamp, duration, and int64 / float64 expressions.  An order
+        column outside the select list is gathered too and not returned
+        (listed and hidden items together stay within 16).  ``limit`` and
+        ``offset`` (non-negative) cut the sorted rows.  After the scan's one
+        sync, whose count sizes them, the launches of a stable radix sort
+        (csrc/kernels/colsort.hip, ops/colsort.py: one 8-bit pass per byte of
+        a column's storage type, one more for its classes) and one gather of
+        every column are enqueued on the emit stream, which the caller's
+        stream then waits for; nothing is synchronized again.  The sort holds
+        24 bytes per selected row on the device while it runs; the outputs
+        are sized for every scanned row as before.  A windowed string
+        column's ``values`` keep the capacity of all selected rows'
+        characters: ``offsets[-1]`` of them are the result's.
+        ``ScanOut.order`` is the normalized [(name, descending)]; ``top``
+        remains the path for small k, allocating nothing of the table's
+        height."""
+        _check_order_args(project, order_by, limit, offset)
         if isinstance(project, (list, tuple)):
-            return self._scan_select(quals, project, batches, join)
+            return self._scan_select(quals, project, batches, join, order_by, limit, offset)
         pattr = project if isinstance(project, JoinAttr) else None
         join = _check_join(self.meta, join, pattr)
         if pattr is not None:
@@ -1907,12 +1942,17 @@ class ArrowScan:
                        column=pmeta, dictionary=pdict, offsets=offsets,
                        exprs=[x.prog for x in run.exprs])
 
-    def _scan_select(self, quals, project, batches, join) -> ScanOut:
+    def _scan_select(self, quals, project, batches, join, order_by=None, limit=None,
+                     offset=0) -> ScanOut:
         """scan_where with a select list: the stages of the single form up to
         the emit, which writes the row ids and every column of the list in
         one walk of each group's bitmap (ops/colproject.py), on the emit
         stream, in group order, behind the shared cursors."""
         items = _select_items(project)
+        keys = SO.order_keys(order_by) if order_by is not None else None
+        nvis = len(items)
+        items = _with_hidden(items, keys)
+        order = [(str(n), d) for n, d in keys] if keys else None
         attrs = [it for it in items if isinstance(it, JoinAttr)]
         join = _check_join(self.meta, join, attrs)
         cl = _named_clauses(quals) if (quals or join is None) else []
@@ -1920,6 +1960,7 @@ class ArrowScan:
         pnames = [it for it in items if not isinstance(it, JoinAttr)]
         names = _scanned(cl, join, pnames)
         xm = _with_exprs(self.meta, names)
+        _order_columns(xm, keys)
         metas = _select_meta(xm, items)
         names, full = _split_names(xm, names)
         cols, nrows, groups = self._resolve(names, batches)
@@ -1965,7 +2006,8 @@ class ArrowScan:
             for si, po in zip(sel, outs):
                 po.values = si.out[:0] if si.chars is None else si.chars[:0]
                 po.offsets = self._zero() if si.chars is not None else None
-            return ScanOut(nrows, 0, out[:0], {"total_s": time.perf_counter() - t0}, columns=outs)
+            return ScanOut(nrows, 0, out[:0], {"total_s": time.perf_counter() - t0},
+                           columns=outs[:nvis], order=order)
         ptr = lambda x: x.data_ptr() if x is not None else 0
         desc = PJ.proj_cols([(si.kind, si.width, ptr(si.out), ptr(si.valid), ptr(si.chars),
                               ptr(si.cursor)) for si in sel])
@@ -1990,9 +2032,73 @@ class ArrowScan:
             else:
                 po.values = si.out[:count]
         secs["timeline_ms"] = [(k, e, round((t - t_alloc) * 1e3, 3)) for k, e, t in run.marks]
-        return ScanOut(nrows, int(count), out[:count], secs, bytes_read=run.bytes_read,
+        indices, errs = out[:count], None
+        if keys:
+            t_sort = time.perf_counter()
+            indices, errs = self._sort_select(keys, items, metas, sel, outs, out, int(count),
+                                              limit, offset)
+            secs["sort_s"] = time.perf_counter() - t_sort
+            secs["total_s"] += secs["sort_s"]
+        return ScanOut(nrows, int(count), indices, secs, bytes_read=run.bytes_read,
                        column_bytes=run.column_bytes, groups=len(groups),
-                       exprs=[x.prog for x in run.exprs], columns=outs)
+                       exprs=[x.prog for x in run.exprs], columns=outs[:nvis], order=order,
+                       sort_errors=errs)
+
+    def _sort_select(self, keys, items, metas, sel: List[_SelItem], outs: List[ProjOut],
+                     rows: torch.Tensor, n: int, limit, offset) -> tuple:
+        """order_by=: the n selected rows the emit left (``rows``, ``sel``,
+        ``outs``) sorted by ``keys`` and cut to the window, every ProjOut
+        replaced by its gathered copy.  The launches go to the emit stream;
+        the current stream waits for them on the device.  Returns (the row
+        ids in result order, the gather's error word)."""
+        first, cnt = SO.window(n, limit, offset)
+        new = lambda *shape, dtype: torch.empty(*shape, dtype=dtype, device=self.device)
+        ids = new(max(cnt, 1), dtype=torch.int64)
+        st = SO.State(n, self.device)
+        if n == 0:
+            return ids[:0], st.err
+        at = {str(it): k for k, it in enumerate(items) if not isinstance(it, JoinAttr)}
+        order = [(T.TYPE_CODE[metas[at[str(nm)]].storage], sel[at[str(nm)]].out,
+                  sel[at[str(nm)]].valid, desc) for nm, desc in keys]
+        specs, strs = [], []
+        for si, po in zip(sel, outs):
+            v = new(max(cnt, 1), dtype=torch.uint8) if si.valid is not None else None
+            if si.chars is not None:
+                # the permuted lengths behind a leading zero: their running sum
+                # is the output offsets
+                off = torch.zeros(cnt + 1, dtype=torch.int64, device=self.device)
+                ch = new(max(po.values.numel(), 4), dtype=torch.uint8)
+                specs.append((SO.LEN, 0, si.out.data_ptr(), off[1:].data_ptr(),
+                              si.valid.data_ptr() if v is not None else 0,
+                              v.data_ptr() if v is not None else 0))
+                strs.append((si, po, off, ch))
+                po.offsets = off
+            else:
+                o = new((max(cnt, 1),) + tuple(si.out.shape[1:]), dtype=si.out.dtype)
+                width = si.out.element_size() * (2 if si.out.dim() == 2 else 1)
+                specs.append((SO.FIXED, width, si.out.data_ptr(), o.data_ptr(),
+                              si.valid.data_ptr() if v is not None else 0,
+                              v.data_ptr() if v is not None else 0))
+                po.values = o[:cnt]
+            po.valid = v[:cnt] if v is not None else None
+        if cnt == 0:
+            # an empty window: nothing to order, nothing to gather
+            for si, po, off, ch in strs:
+                po.values = ch[:0]
+            return ids[:0], st.err
+        es = self._emit_stream()
+        cur = torch.cuda.current_stream(self.device)
+        es.wait_stream(cur)
+        with torch.cuda.stream(es):
+            SO.order(st, order, stream=es)
+            SO.apply(st.order, n, first, cnt, rows, ids, SO.sort_cols(specs), st.err, stream=es)
+            for si, po, off, ch in strs:
+                off[1:].cumsum_(0)
+                SO.chars(st.order, n, first, cnt, si.out, si.chars, po.values.numel(), off, ch,
+                         stream=es)
+                po.values = ch[:po.values.numel()]
+        cur.wait_stream(es)
+        return ids[:cnt], st.err
 
     def aggregate(self, quals, aggs, by=None, batches: Optional[Tuple[int, int]] = None,
                   join: Union[Join, StarJoin, None] = None) -> "AggOut":
@@ -2143,7 +2249,8 @@ class ArrowScan:
         bytes, a dictionary-encoded column's indices (``TopOut.dictionary``
         holds the values) or ``dim[attr]`` of the semi-join.  ``quals`` (may
         be empty), ``batches`` and ``join`` as in scan_where.  One order
-        column, no OFFSET.  ``order_by`` (and ``project``, and a qualifier's
+        column, no OFFSET: ``scan_where(order_by=, limit=)`` sorts by several
+        columns and serves k beyond MAX_K.  ``order_by`` (and ``project``, and a qualifier's
         column) may be an expression (ops/colexpr.E), computed on the device
         per group: a float64 one orders its NaNs and nulls as a stored column's.
         See TopOut."""
@@ -2212,12 +2319,14 @@ class ArrowScan:
     filter = scan
 
     def host_scan_where(self, quals, project=None, batches: Optional[Tuple[int, int]] = None,
-                        join: Union[Join, StarJoin, None] = None) -> "HostScanOut":
+                        join: Union[Join, StarJoin, None] = None, order_by=None,
+                        limit: Optional[int] = None, offset: int = 0) -> "HostScanOut":
         """The same query on the CPU (buffers read with pread, decoded by
         the decoders' host twins, predicates by colpred's numpy twin, the
         join by coljoin's)."""
         return host_scan_where(self.path, quals, project, batches, meta=self.meta,
-                               dicts=self._dicts, join=join)
+                               dicts=self._dicts, join=join, order_by=order_by, limit=limit,
+                               offset=offset)
 
     def _free_slots(self) -> None:
         if self._slots:
@@ -2246,6 +2355,7 @@ class HostScanOut:
     # project=[...]: one ProjOut of numpy arrays per item, laid out as the
     # device scan's (values / valid / dictionary above are then None)
     columns: Optional[List[ProjOut]] = None
+    order: Optional[List[Tuple[str, bool]]] = None   # order_by=, normalized
 
     def to_arrow(self):
         """The select list's columns as a pyarrow.Table (ScanOut.to_arrow)."""
@@ -2254,17 +2364,63 @@ class HostScanOut:
         return _arrow_table(self.columns)
 
 
+def _check_order_args(project, order_by, limit, offset) -> None:
+    """What scan_where / host_scan_where take of order_by / limit / offset,
+    checked before anything else."""
+    SO.window(0, limit, offset)
+    if order_by is None:
+        if limit is not None or offset:
+            raise ValueError("limit= / offset= cut a sorted result: they need order_by=")
+        return
+    if not isinstance(project, (list, tuple)):
+        raise ValueError("order_by= needs the list form of project= (project=[...]): the sort "
+                         "gathers a select list's columns")
+
+
+def _with_hidden(items: list, keys) -> list:
+    """The select list followed by the order columns it does not name."""
+    if not keys:
+        return items
+    shown = [str(it) for it in items if not isinstance(it, JoinAttr)]
+    items = items + [n for n, _ in keys if str(n) not in shown]
+    if len(items) > PJ.MAX_COLS:
+        raise NotImplementedError(f"a select list of {len(shown)} columns and {len(items)} with "
+                                  f"the order columns outside it: at most {PJ.MAX_COLS} are "
+                                  "gathered in one emit pass")
+    return items
+
+
+def _order_columns(meta, keys) -> None:
+    """The order columns' kinds, checked before anything is read: what
+    ``top`` orders."""
+    schema = {c.name: c for c in meta.schema}
+    for name, _ in keys or []:
+        if name not in schema:
+            raise ValueError(f"no column {str(name)!r}")
+        c = schema[name]
+        if c.dictionary is not None or c.kind not in ("int", "float") + _TEMPORAL or \
+                c.storage not in T.TYPE_CODE:
+            kind = "dictionary-encoded" if c.dictionary is not None else c.kind
+            raise NotImplementedError(f"ORDER BY {name}: {kind} columns are not ordered on the "
+                                      "GPU (integer, float32/64, date, time, timestamp and "
+                                      "duration columns are)")
+
+
 def _host_select(path: str, quals, project, batches, meta: ArrowFile, dicts: dict,
-                 join) -> HostScanOut:
+                 join, order_by=None, limit=None, offset=0) -> HostScanOut:
     """host_scan_where with a select list: every column gathered per record
     batch with the rows the qualifiers and the join select, in the layout of
     the device scan's ProjOut."""
     items = _select_items(project)
+    keys = SO.order_keys(order_by) if order_by is not None else None
+    nvis = len(items)
+    items = _with_hidden(items, keys)
     attrs = [it for it in items if isinstance(it, JoinAttr)]
     join = _check_join(meta, join, attrs)
     cl = _named_clauses(quals) if (quals or join is None) else []
     pnames = [it for it in items if not isinstance(it, JoinAttr)]
     meta = _with_exprs(meta, [p.col for c in cl for p in c] + pnames)
+    _order_columns(meta, keys)
     metas = _select_meta(meta, items)
     base = np.concatenate([[0], np.cumsum(meta.rows)]).astype(np.int64)
     nrows = 0
@@ -2316,8 +2472,20 @@ def _host_select(path: str, quals, project, batches, meta: ArrowFile, dicts: dic
             po.values = np.zeros((0, 2), np.int64) if st == "d16" else \
                 np.zeros(0, np.uint8 if st == "b1" else st)
         cols.append(po)
-    return HostScanOut(nrows, np.concatenate(ids) if ids else np.zeros(0, np.int64),
-                       exprs=list(getattr(meta, "progs", {}).values()), columns=cols)
+    rows = np.concatenate(ids) if ids else np.zeros(0, np.int64)
+    if keys:
+        # the twin's order (coltopk's encoding, np.lexsort), then every column
+        at = {str(it): k for k, it in enumerate(items) if not isinstance(it, JoinAttr)}
+        perm = SO.host_order([(cols[at[str(n)]].values, cols[at[str(n)]].valid, d)
+                              for n, d in keys], len(rows))
+        first, cnt = SO.window(len(rows), limit, offset)
+        rows = rows[perm[first:first + cnt]]
+        for po in cols:
+            po.values, po.valid, po.offsets = SO.host_apply(perm, first, cnt, po.values, po.valid,
+                                                            po.offsets)
+    return HostScanOut(nrows, rows, exprs=list(getattr(meta, "progs", {}).values()),
+                       columns=cols[:nvis],
+                       order=[(str(n), d) for n, d in keys] if keys else None)
 
 
 def _order_name(order_by):
@@ -2439,15 +2607,18 @@ def _host_batches(path: str, meta: ArrowFile, dicts: dict, cl, join,
 
 def host_scan_where(path: str, quals, project=None,
                     batches: Optional[Tuple[int, int]] = None, meta: Optional[ArrowFile] = None,
-                    dicts: Optional[dict] = None, join: Union[Join, StarJoin, None] = None) -> HostScanOut:
+                    dicts: Optional[dict] = None, join: Union[Join, StarJoin, None] = None,
+                    order_by=None, limit: Optional[int] = None, offset: int = 0) -> HostScanOut:
     """ArrowScan.scan_where on the CPU: the same metadata, the same
     compiled predicates (ops/colpred.py), evaluated by the kernel's numpy
     twin over buffers decoded by the GPU decoders' host twins.  The
     reference point for the GPU path and a scan for machines without one."""
+    _check_order_args(project, order_by, limit, offset)
     meta = meta if meta is not None else read_metadata(path)
     dicts = dicts if dicts is not None else {}
     if isinstance(project, (list, tuple)):
-        return _host_select(path, quals, project, batches, meta, dicts, join)
+        return _host_select(path, quals, project, batches, meta, dicts, join, order_by, limit,
+                            offset)
     pattr = project if isinstance(project, JoinAttr) else None
     join = _check_join(meta, join, pattr)
     if pattr is not None:

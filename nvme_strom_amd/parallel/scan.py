@@ -134,9 +134,14 @@ class DistributedArrowScan:
 
     # ---- scan -------------------------------------------------------------
     def scan_where(self, quals: Sequence[Tuple[str, object, object]],
-                   project: Optional[str] = None, gather: str = "all") -> DistScanOut:
+                   project: Optional[str] = None, gather: str = "all", order_by=None,
+                   limit=None, offset=0) -> DistScanOut:
         if gather not in ("all", "none"):
             raise ValueError(f"gather {gather!r}")
+        if order_by is not None or limit is not None or offset:
+            raise NotImplementedError("order_by= / limit= / offset=: merging sorted results "
+                                      "across ranks is not wired; ArrowScan.scan_where sorts on "
+                                      "a single GPU")
         if isinstance(project, (list, tuple)):
             raise NotImplementedError("a select list (project=[...]) is not gathered across "
                                       "ranks: ArrowScan.scan_where takes one on a single GPU; "

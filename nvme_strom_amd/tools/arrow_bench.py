@@ -637,6 +637,70 @@ def expr_row(path: str, fd: int, a, col) -> dict:
     return row
 
 
+def order_row(path: str, fd: int, a, col) -> dict:
+    """The select query (``project=["id", "x", "val"]``) with and without
+    ``order_by=[("val", "descending"), "x"]`` on the same file, alternated,
+    the file evicted before every scan and the device synchronized after it
+    (the sort's launches are enqueued, not waited for, by the scan itself).
+    Reports both medians and the sort stage's share of the ordered scan; the
+    order is verified against numpy's lexsort."""
+    import torch
+
+    import nvme_strom_amd as S
+    from nvme_strom_amd.models.arrow_scan import ArrowScan
+    quals = [("val", 100_000, 599_999), ("x", 0.25, 0.75)]
+    names = ["id", "x", "val"]
+    order_by = [("val", "descending"), "x"]
+    sc = ArrowScan(path, "cuda", slot_bytes=a.slot_mib << 20, nslots=a.nslots or None,
+                   chunk_sz=(a.chunk_kib << 10) or None)
+
+    def timed(**kw):
+        S.evict_file(fd)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        out = sc.scan_where(quals, project=names, **kw)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, out
+    plain_s, order_s = [], []
+    try:
+        timed()                                                  # cold: plans, slots, code
+        timed(order_by=order_by)
+        for k in range(max(1, a.agg_pairs)):
+            for what in (("plain", "order") if k % 2 == 0 else ("order", "plain")):
+                if what == "plain":
+                    plain_s.append(timed()[0])
+                else:
+                    dt, out = timed(order_by=order_by)
+                    order_s.append(dt)
+            _log(f"order pair {k}: plain {plain_s[-1] * 1e3:.1f} ms, ordered "
+                 f"{order_s[-1] * 1e3:.1f} ms")
+    finally:
+        sc.close()
+    m = None
+    for name, lo, hi in quals:
+        vals, valid = col(name)
+        mm = (vals >= lo) & (vals <= hi)
+        if valid is not None:
+            mm &= valid
+        m = mm if m is None else m & mm
+    ref = np.flatnonzero(m)
+    ref = ref[np.lexsort((col("x")[0][ref], -col("val")[0][ref].astype(np.int64)))]
+    ok = bool(np.array_equal(out.indices.cpu().numpy(), ref)) and \
+        int(out.sort_errors.item()) == 0
+    for n, c in zip(names, out.columns):
+        ok = ok and bool(np.array_equal(c.values.cpu().numpy(), col(n)[0][ref]))
+    mp, mo = float(np.median(plain_s)), float(np.median(order_s))
+    row = dict(project=names, order_by=[list(o) if isinstance(o, tuple) else o for o in order_by],
+               quals=[repr(q) for q in quals], selected=out.selected, verified=ok,
+               plain_ms=[round(x * 1e3, 2) for x in plain_s],
+               ordered_ms=[round(x * 1e3, 2) for x in order_s],
+               plain_median_ms=round(mp * 1e3, 2), ordered_median_ms=round(mo * 1e3, 2),
+               sort_share_of_ordered_scan=round(max(mo - mp, 0.0) / mo, 4),
+               sort_enqueue_s=round(out.seconds.get("sort_s", 0.0), 5))
+    _log(json.dumps(row))
+    return row
+
+
 def select_row(path: str, fd: int, a, col) -> dict:
     """``SELECT id, x, val WHERE val BETWEEN .. AND x BETWEEN ..`` as one
     select-list scan (``project=["id", "x", "val"]``: one emit pass,
@@ -911,6 +975,9 @@ def main(argv=None) -> int:
     ap.add_argument("--select", action="store_true",
                     help="add the select-list row: scan_where(qual2, project=[id, x, val]) "
                          "alternated with the three single-column scans (--agg-pairs pairs)")
+    ap.add_argument("--order-by", action="store_true",
+                    help="add the ORDER BY row: the select query with and without "
+                         "order_by=[(val, descending), x], alternated")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     import torch
@@ -1030,6 +1097,8 @@ def main(argv=None) -> int:
             res["expr"] = expr_row(path, fd, a, col)
         if a.select:
             res["select"] = select_row(path, fd, a, col)
+        if a.order_by:
+            res["order_by"] = order_row(path, fd, a, col)
     finally:
         os.close(fd)
     if a.hashagg:

@@ -44,7 +44,8 @@ def main(argv=None):
                          "like (column_qual_like: LIKE / contains / endswith next to the string "
                          "equality and prefix qualifiers, short words and long rows), "
                          "rows_multi (bitmap_to_rows_multi: a select list in one emit pass next "
-                         "to the single-column emit kernels once per column)")
+                         "to the single-column emit kernels once per column), "
+                         "sort (the ORDER BY radix sort next to torch.sort, 2^24 and 2^26 keys)")
     ap.add_argument("--out", default="")
     a = ap.parse_args(argv)
     only = set(a.only.split(","))
@@ -204,11 +205,84 @@ def main(argv=None):
         _like_rows(n, dev, log)
     if "rows_multi" in only:
         _rows_multi_rows(dev, log, res)
+    if "sort" in only:
+        _sort_rows(dev, res)
     js = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:
             f.write(js)
     print(js)
+
+
+def _sort_rows(dev, res, sizes=(1 << 24, 1 << 26), reps=5, hbm_peak=8.0e12):
+    """The radix sort (colsort.hip: encode + one pass per key byte) next to
+    ``torch.sort(keys, stable=True)`` on the same device, alternated, ``reps``
+    repetitions each, median and spread: int32 / int64 / float64 uniform
+    keys, int64 already sorted and all equal, and two columns (int8 with ties,
+    then float64).  The permutation is checked against torch.sort's indices
+    before anything is timed.  Bytes: 36 per row and pass (key and permutation
+    read by the histogram and the scatter, written once), as a share of the
+    HBM peak of 8 TB/s."""
+    from nvme_strom_amd.ops import colsort as SO
+
+    def once(fn):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        s.record()
+        fn()
+        e.record()
+        torch.cuda.synchronize()
+        return s.elapsed_time(e) / 1e3
+
+    g = torch.Generator(device=dev)
+    g.manual_seed(3)
+    for n in sizes:
+        u = lambda dt: torch.randint(-2**31, 2**31 - 1, (n,), dtype=dt, device=dev, generator=g)
+        i64 = u(torch.int64) * 2654435761
+        cases = {"i32_uniform": [u(torch.int32)], "i64_uniform": [i64],
+                 "f64_uniform": [torch.randn(n, dtype=torch.float64, device=dev, generator=g)],
+                 "i64_sorted": [torch.arange(n, dtype=torch.int64, device=dev)],
+                 "i64_equal": [torch.full((n,), 7, dtype=torch.int64, device=dev)],
+                 "i8_ties+f64": [torch.randint(0, 6, (n,), dtype=torch.int8, device=dev,
+                                               generator=g),
+                                 torch.randn(n, dtype=torch.float64, device=dev, generator=g)]}
+        st = SO.State(n, dev)
+        for name, keys in cases.items():
+            cols = [(SO.TYPE_CODE[f"{'f' if k.is_floating_point() else 'i'}{k.element_size()}"],
+                     k, None, False) for k in keys]
+
+            def ours():
+                st.cur, st.fresh = 0, True
+                return SO.order(st, cols)
+
+            def theirs():
+                # a stable sort by the last column, then by the first
+                idx = None
+                for k in reversed(keys):
+                    j = torch.sort(k if idx is None else k[idx], stable=True)[1]
+                    idx = j if idx is None else idx[j]
+                return idx
+            npass = ours()
+            want = theirs()
+            if not torch.equal(st.order.view(torch.int32).to(torch.int64) & 0xFFFFFFFF, want):
+                raise RuntimeError(f"sort {name} n={n}: the permutation differs from torch.sort's")
+            del want
+            ta, tb = [], []
+            for _ in range(reps):
+                ta.append(once(ours))
+                tb.append(once(theirs))
+            med = lambda t: float(np.median(t))
+            moved = 36 * n * npass
+            res[f"sort_{name}_n{n}"] = dict(
+                passes=npass, ms=round(med(ta) * 1e3, 3),
+                ms_min_max=[round(min(ta) * 1e3, 3), round(max(ta) * 1e3, 3)],
+                Mrows_s=round(n / med(ta) / 1e6, 1), GBps=round(moved / med(ta) / 1e9, 1),
+                hbm_peak_share=round(moved / med(ta) / hbm_peak, 3),
+                torch_ms=round(med(tb) * 1e3, 3),
+                torch_ms_min_max=[round(min(tb) * 1e3, 3), round(max(tb) * 1e3, 3)],
+                torch_Mrows_s=round(n / med(tb) / 1e6, 1))
+            print(f"sort_{name}_n{n}", res[f"sort_{name}_n{n}"], file=sys.stderr, flush=True)
+        del st, cases
 
 
 def _rows_multi_rows(dev, log, res, rows=1 << 25):

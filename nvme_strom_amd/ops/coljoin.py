@@ -98,12 +98,15 @@ class HostTable:
         return int(self.words[H_MAXDISP])
 
     def items(self) -> dict:
-        """{key: payload} of everything in the table."""
+        """{key: payload} of everything in the table (the payload as the
+        int32 a lookup returns)."""
         s = self.slots
         used = s[:, 0] != EMPTY
-        out = dict(zip(s[used, 0].view(np.int64).tolist(), s[used, 1].astype(np.int64).tolist()))
+        pay = s[used, 1].astype(np.uint32).view(np.int32)
+        out = dict(zip(s[used, 0].view(np.int64).tolist(), pay.tolist()))
         if self.words[H_HAS_EMPTY]:
-            out[-(1 << 63)] = int(self.words[H_EMPTY_PAYLOAD])
+            out[-(1 << 63)] = int(self.words[H_EMPTY_PAYLOAD:H_EMPTY_PAYLOAD + 1]
+                                  .astype(np.uint32).view(np.int32)[0])
         return out
 
     def true_maxdisp(self) -> int:
